@@ -16,6 +16,27 @@ Usage:
 For N > 1 launch via:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print one JSON result line.  Two options add to that:
+
+  --dump-outputs DIR   after the timed steps, rank 0 writes what the last
+                       timed round produced as DIR/<name>.npy, so two
+                       builds can be compared output for output (inputs
+                       are seeded: same arguments, same inputs):
+                         stats.npy   float64 [len(STATS_KEYS)+1]: the
+                                     round's stats in STATS_KEYS order,
+                                     then the stop flag
+                         params.npy  float32: flat policy parameters
+                                     after the round's update
+                         obs.npy     float32: env observations the round
+                                     left behind (input of the next one)
+                       Arrays above DUMP_MAX_ELEMS elements are written
+                       as a fixed, seeded sample of their elements.
+  --full               secondary measurements (anything beyond the
+                       headline figure belongs behind this switch).  The
+                       benchmark has none at present, so a --full run
+                       equals a plain one.
 """
 
 from __future__ import annotations
@@ -25,6 +46,7 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 
 from dppo_amd.config import DPPOConfig
@@ -69,6 +91,37 @@ PRESETS = {
     ),
 }
 
+# order of the train_round() stats in stats.npy (the stop flag follows)
+STATS_KEYS = (
+    "l_mul", "best_rank", "score", "epr_max", "epr_mean",
+    "policyLoss", "entropyLoss", "valueLoss", "total_loss",
+)
+# per-array cap for --dump-outputs: 3 arrays x 4M x 4 B = 48 MB at most
+DUMP_MAX_ELEMS = 4 * 1024 * 1024
+DUMP_SAMPLE_SEED = 20240229
+
+
+def _dump_array(t: torch.Tensor) -> np.ndarray:
+    """float32 host copy of `t`, flattened; above DUMP_MAX_ELEMS a fixed
+    seeded sample of its elements (same indices for the same numel)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randint(flat.numel(), (DUMP_MAX_ELEMS,), generator=g)
+        flat = flat[idx.sort().values.to(flat.device)]
+    return flat.to(device="cpu", dtype=torch.float32).numpy()
+
+
+def dump_outputs(out_dir: str, engine: DPPOEngine, stats, stop: bool) -> None:
+    os.makedirs(out_dir, exist_ok=True)
+    missing = set(stats) ^ set(STATS_KEYS)
+    assert not missing, f"train_round() stats changed: {sorted(missing)}"
+    row = [float(stats[k]) for k in STATS_KEYS] + [float(stop)]
+    np.save(os.path.join(out_dir, "stats.npy"), np.asarray(row, np.float64))
+    np.save(os.path.join(out_dir, "params.npy"),
+            _dump_array(engine.flat_pi.flat_param))
+    np.save(os.path.join(out_dir, "obs.npy"), _dump_array(engine.obs))
+
 
 def main() -> None:
     p = argparse.ArgumentParser()
@@ -79,7 +132,13 @@ def main() -> None:
     p.add_argument("--num-envs", type=int, default=None)
     p.add_argument("--rollout", type=int, default=None)
     p.add_argument("--device", type=str, default=None)
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write the last timed round's outputs as DIR/*.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (none today)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     n_gpus = max(args.gpus, world)
@@ -114,7 +173,7 @@ def main() -> None:
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        engine.train_round()
+        last = engine.train_round()
     sync()
     elapsed = time.perf_counter() - t0
 
@@ -125,6 +184,9 @@ def main() -> None:
 
         dist.all_reduce(e_t, op=dist.ReduceOp.MAX)
     elapsed = float(e_t)
+
+    if args.dump_outputs and comm.rank == 0:
+        dump_outputs(args.dump_outputs, engine, *last)
 
     E, T = cfg.NUM_ENVS, cfg.MAX_EPOCH_STEPS
     env_steps = E * T * args.steps * world
