@@ -92,7 +92,7 @@ void gemm_env_step(torch::Tensor xva, torch::Tensor M, torch::Tensor xin,
                    torch::Tensor epr,
                    torch::Tensor rewards, torch::Tensor dones,
                    torch::Tensor rsum, torch::Tensor seed_dev, double sigma,
-                   int64_t step);
+                   int64_t step, torch::Tensor V, torch::Tensor xvp);
 
 void rollout_env_step(torch::Tensor xin, torch::Tensor xout, torch::Tensor G,
                       torch::Tensor envd, torch::Tensor horizons,
@@ -154,8 +154,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("rollout_sample", &rollout_sample,
           "per-step action sampling + eps-greedy (v3 rollout) (gfx950)");
   mod.def("gemm_env_step", &gemm_env_step,
-          "fused G-GEMM + env transition epilogue + per-env finish "
-          "(v3 rollout; gfx950)");
+          "fused G-GEMM + env transition epilogue + per-env finish, "
+          "optionally folding the next step's x@V (v3 rollout; gfx950)");
   mod.def("rollout_env_step", &rollout_env_step,
           "per-step synthetic env finish: tanh/reward/done/reset (gfx950)");
   mod.def("rollout_moments", &rollout_moments,

@@ -33,6 +33,13 @@ DEV_INLINE float fast_tanhf(float x) {
   return 1.0f - 2.0f / (e + 1.0f);
 }
 
+// x^2+y^2+z^2+w^2 with the contraction spelled out: the split and fused
+// env-step kernels must round the reward's chunk sums identically.
+DEV_INLINE float sq4(float4 v) {
+  return __fmaf_rn(v.w, v.w,
+                   __fmaf_rn(v.z, v.z, __fmaf_rn(v.y, v.y, __fmul_rn(v.x, v.x))));
+}
+
 DEV_INLINE int64_t gidx() {
   return static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
 }

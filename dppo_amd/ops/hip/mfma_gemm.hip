@@ -41,6 +41,7 @@
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int BK = 16;        // K-step per stage
 constexpr int M_WAVE = 32;    // rows per wave tile
@@ -75,13 +76,16 @@ struct FwdArgs {
   int ablate;         // perf diagnosis only (wrong results when nonzero):
                       // 1 skip X stage, 2 skip W stage, 4 skip MFMA,
                       // 8 skip epilogue stores
-  // activation 5 (fused env step, v3 rollout): the G = [XV|a] @ [U;B]
-  // GEMM's epilogue computes the env transition directly —
-  // pred = tanh(x*d + acc + sigma*noise), out = done ? fresh : pred —
-  // writing the new env state and the next recorded state, and
-  // accumulating per-env pred^2 partials for the reward.  Kills the
-  // 2x[E][D] G round trip and most of env_finish_kernel (round-2 lever
-  // #3, profiles/r01_final_v3_69M.txt).  RNG slots == env_finish's.
+  // activation 5 (fused env step, v3 rollout; gemm_fwd_glds_kernel's ENV
+  // instantiation): the G = [XV|a] @ [U;B] GEMM's epilogue computes the
+  // env transition directly — pred = tanh(x*d + acc + sigma*noise),
+  // out = done ? fresh : pred — writing the next recorded state and
+  // per-(panel, env) pred^2 partials for the reward.  The accumulators
+  // are repacked through LDS into env_finish_kernel's float4-per-lane
+  // layout, so the per-element work, RNG slots and results are that
+  // kernel's; the [E][D] G write + read never happen.  With env_xvp set
+  // the block also multiplies its finished next-state tile by its rows
+  // of V (the next step's x@V, per-panel partials).
   const float* env_xin;     // [E][D] state at `step`
   float* env_x;             // [E][D] out: state at `step`+1 (the v3 loop
                             // passes the states-blob slot directly; may
@@ -92,6 +96,8 @@ struct FwdArgs {
   const long long* seed_dev;
   float* env_rsum;          // [npanels][E] per-panel pred^2 partials
                             // (plain stores — deterministic, no zeroing)
+  const float* env_V;       // [D][16] x@V fold operand (null: no fold)
+  float* env_xvp;           // [npanels][E][16] next-state @ V partials
   float sigma;
   int step;
 };
@@ -499,10 +505,13 @@ __global__ void gemm_fwd_pipe_kernel(FwdArgs a) {
 // address (guide rule 21) — same 64 B cacheline, zero coalescing cost.
 // ---------------------------------------------------------------------------
 
-template <int RING>  // ring depth: 2 (24 KB, 6 blocks/CU — overlap via
-                     // MORE co-resident blocks), 3 (36 KB, 4 blocks/CU,
-                     // default), 4 (48 KB, 3 blocks/CU — deeper
-                     // in-flight staging; measured slower)
+template <int RING,   // ring depth: 2 (24 KB, 6 blocks/CU — overlap via
+                      // MORE co-resident blocks), 3 (36 KB, 4 blocks/CU,
+                      // default), 4 (48 KB, 3 blocks/CU — deeper
+                      // in-flight staging; measured slower)
+          bool ENV = false>  // fused env-step epilogue (activation 5) — its
+                             // own instantiation, so the layer GEMMs'
+                             // registers and occupancy do not see it
 __launch_bounds__(FWD_WAVES * 64, RING == 2 ? 6 : RING == 3 ? 4 : 3)
 __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
   constexpr int NT = 2;
@@ -629,45 +638,157 @@ __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
-  if (a.activation == 5) {
-    // fused env step: pred = tanh(x*d + acc + sigma*noise);
-    // out = done ? fresh-seed : pred; reward partials via one atomic per
-    // (row, 32-lane half).  RNG slots match env_finish_kernel exactly.
+  if constexpr (ENV) {
+    // Fused env step.  The accumulator layout (lane = column) would make
+    // every element pay a whole Box-Muller pair and move x/d/x' as 4-B
+    // scalars, so the tile is repacked through the (now dead) ring LDS
+    // into env_finish_kernel's layout: one float4 = 4 consecutive dims of
+    // one row per lane, two noise pairs per float4, b128 global traffic.
+    //
+    // Each wave repacks its own 32 rows in two passes of 16 rows x 64
+    // cols (accumulator registers 8h..8h+7 of both column tiles are rows
+    // 16h..16h+15), 4 KB per wave and 16 KB per block — inside the 24 KB
+    // of the 2-deep ring, and no block barrier: a wave only ever touches
+    // its own image, and its LDS operations complete in order.
+    //
+    // Image: row stride 64 floats (one 256-B bank row), float4 slot s of
+    // row i stored at slot s ^ i.
+    //   - ds_write_b32 of one accumulator register: a 32-lane half writes
+    //     32 consecutive columns of one row; the XOR permutes whole
+    //     16-B slots inside the row, so the 32 dwords stay on 32 distinct
+    //     banks (mod 32).
+    //   - ds_read_b128, lane l -> (row 4j + l/16, slot l%16): each of the
+    //     instruction's 16-lane groups ({0-3,12-15,20-27}, ...) takes 8
+    //     slots of one row and the complementary 8 of the next; rows i
+    //     and i^1 XOR them with values that differ in bit 0 only, which
+    //     maps the two 8-slot sets onto disjoint slots — all 64 banks
+    //     once.
+    //   - the fold's A fragments (below) read b128 at (row l%16, slot
+    //     (4q + l/16) ^ row): per 16-lane group the 16 (row, slot) pairs
+    //     land on 16 distinct slots, again conflict-free.  An unswizzled
+    //     image would put all 16 rows of a column on one bank.
+    constexpr int HR = 16;  // rows per wave per pass
+    static_assert(RING * SLOT >= FWD_WAVES * HR * NW * 4 + NW * 16 * 4,
+                  "env epilogue image + V panel must fit the ring");
+    float* tile = reinterpret_cast<float*>(smem) + wave * (HR * NW);
+    float* vs = reinterpret_cast<float*>(smem) + FWD_WAVES * HR * NW;
+    const bool fold = a.env_xvp != nullptr;
+    if (fold) {
+      // this panel's rows of V ([64][16], pad rows zero) -> LDS, one
+      // float4 per thread.  Rows 4..7 of every 8 swap with their odd/even
+      // neighbour: the B fragment's two lane groups of a 32-lane half
+      // read rows k and k+4, 64 floats apart = the same 32-bank window.
+      const int kl = tid >> 2;
+      const int kr = n0 + kl;
+      float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (kr < a.N)
+        vv = *reinterpret_cast<const float4*>(
+            &a.env_V[(int64_t)kr * 16 + 4 * (tid & 3)]);
+      *reinterpret_cast<float4*>(
+          &vs[(kl ^ ((kl >> 2) & 1)) * 16 + 4 * (tid & 3)]) = vv;
+      __syncthreads();
+    }
     const unsigned seed = (unsigned)(*a.seed_dev);
+    const float sigma = a.sigma;
+    const int step = a.step;
+    const int c4 = lane & 15;   // float4 slot inside the 64-col panel
+    const int rsub = lane >> 4;
+    const int d = n0 + 4 * c4;  // first of this lane's 4 dims
+    const int c = d >> 2;       // env_finish_kernel's float4 chunk index
+    const bool cok = d < a.N;   // N%4==0: a float4 is all in or all out
+    float4 dv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (cok) dv = *reinterpret_cast<const float4*>(&a.envd[d]);
     #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int64_t row = b0 + wave * M_WAVE + cd_row(r, lane);
-      const bool rok = row < a.B;
-      const int done =
-          rok ? (a.tcount[row] + 1 >= a.horizons[row] ? 1 : 0) : 0;
-      float part = 0.f;
+    for (int h = 0; h < 2; ++h) {
+      // opaque copy of the lane id: without it the 16 dump addresses of
+      // pass 0 are kept live for pass 1 and the allocator spills them
+      // (80-VGPR budget at 6 blocks/CU); recomputing costs one XOR each
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
       #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        const int col = n0 + t * M_WAVE + i_l;
-        if (rok && col < a.N) {
-          const float dv = a.envd[col];
-          const float xv = a.env_xin[row * a.N + col];
-          float nz = 0.f;
-          if (a.sigma != 0.f) {
-            const float2 pr =
-                g_rng_normal2(seed, (int)row, a.step, 1000 + (col >> 1));
-            nz = (col & 1) ? pr.y : pr.x;
-          }
-          const float pred = fast_tanhf(xv * dv + acc[t][r] + a.sigma * nz);
-          part += pred * pred;
-          const float out =
-              done ? 0.1f * g_rng_normal(seed, (int)row, a.step, 5000 + col)
-                   : pred;
-          a.env_x[row * a.N + col] = out;
+        #pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int lr = cd_row(8 * h + q, ln) - HR * h;
+          const int cc = t * M_WAVE + (ln & 31);
+          tile[lr * NW + ((((cc >> 2) ^ lr) << 2) | (cc & 3))] =
+              acc[t][8 * h + q];
         }
       }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       #pragma unroll
-      for (int off = 16; off > 0; off >>= 1)
-        part += __shfl_down(part, off, 32);
-      // exactly one (wave, r, half) owns each (panel, row): plain store
-      // keeps the reduction deterministic (atomicAdd order is not)
-      if (i_l == 0 && rok)
-        a.env_rsum[(int64_t)blockIdx.y * a.B + row] = part;
+      for (int j = 0; j < 4; ++j) {
+        const int lr = 4 * j + rsub;
+        const int64_t e = b0 + wave * M_WAVE + HR * h + lr;
+        const bool rok = e < a.B;
+        float4* slot =
+            reinterpret_cast<float4*>(&tile[lr * NW + ((c4 ^ lr) << 2)]);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        float ss = 0.f;
+        if (rok && cok) {
+          const float4 gv = *slot;
+          const float4 xv =
+              *reinterpret_cast<const float4*>(&a.env_xin[e * a.N + d]);
+          float nz[4] = {0.f, 0.f, 0.f, 0.f};
+          if (sigma != 0.f) {
+            const float2 p0 = g_rng_normal2(seed, (int)e, step, 1000 + 2 * c);
+            const float2 p1 =
+                g_rng_normal2(seed, (int)e, step, 1000 + 2 * c + 1);
+            nz[0] = p0.x; nz[1] = p0.y; nz[2] = p1.x; nz[3] = p1.y;
+          }
+          v.x = fast_tanhf(xv.x * dv.x + gv.x + sigma * nz[0]);
+          v.y = fast_tanhf(xv.y * dv.y + gv.y + sigma * nz[1]);
+          v.z = fast_tanhf(xv.z * dv.z + gv.z + sigma * nz[2]);
+          v.w = fast_tanhf(xv.w * dv.w + gv.w + sigma * nz[3]);
+          ss = sq4(v);
+          const int done = a.tcount[e] + 1 >= a.horizons[e] ? 1 : 0;
+          if (done) {
+            v.x = 0.1f * g_rng_normal(seed, (int)e, step, 5000 + d);
+            v.y = 0.1f * g_rng_normal(seed, (int)e, step, 5000 + d + 1);
+            v.z = 0.1f * g_rng_normal(seed, (int)e, step, 5000 + d + 2);
+            v.w = 0.1f * g_rng_normal(seed, (int)e, step, 5000 + d + 3);
+          }
+          *reinterpret_cast<float4*>(&a.env_x[e * a.N + d]) = v;
+        }
+        // the 16 lanes of a row hold the whole panel's pred^2: one plain
+        // store per (panel, row) keeps the reward deterministic; chunk
+        // sums, xor tree and env_finish2's ascending panel sum are the
+        // order env_finish_kernel uses too (bitwise-equal rewards)
+        #pragma unroll
+        for (int off = 8; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 16);
+        if (c4 == 0 && rok) a.env_rsum[(int64_t)blockIdx.y * a.B + e] = ss;
+        // fold operand: the state actually written (reset rows included),
+        // zeros in pad columns and rows
+        if (fold) *slot = v;
+      }
+      if (fold) {
+        // x@V fold: [16 rows][64 cols] (LDS) @ V[64][16] on the exact-f32
+        // 16x16x4 MFMA.  The k order inside the sum is free as long as A
+        // and B agree: lane group g = l/16 reads the float4 slot 4q+g and
+        // MFMA (q, m) takes component m of it, i.e. column 4*(4q+g)+m.
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const int fi = lane & 15;
+        f32x4 xa = {0.f, 0.f, 0.f, 0.f};
+        #pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 av = *reinterpret_cast<const float4*>(
+              &tile[fi * NW + (((4 * q + rsub) ^ fi) << 2)]);
+          const float am[4] = {av.x, av.y, av.z, av.w};
+          #pragma unroll
+          for (int m = 0; m < 4; ++m) {
+            const int k = 4 * (4 * q + rsub) + m;
+            const float bv = vs[(k ^ ((k >> 2) & 1)) * 16 + fi];
+            xa = __builtin_amdgcn_mfma_f32_16x16x4f32(am[m], bv, xa, 0, 0, 0);
+          }
+        }
+        // D reg r: row 4*(l/16) + r, col l%16
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t e = b0 + wave * M_WAVE + HR * h + 4 * rsub + r;
+          if (e < a.B)
+            a.env_xvp[((int64_t)blockIdx.y * a.B + e) * 16 + fi] = xa[r];
+        }
+      }
     }
     return;
   }
@@ -730,6 +851,26 @@ __global__ void env_finish2_kernel(const float* __restrict__ rsum,
     }
     epr[e] = ep;
     t[e] = tc;
+  }
+}
+
+// x@V fold: sum the per-panel next-state @ V partials into the concat
+// buffer's first 16 columns (the NEXT step's x@V; the G-GEMM that read
+// xva for this step has finished in stream order).  Thread per
+// (env, float4); fixed panel order, so deterministic.
+__global__ void env_xv_reduce_kernel(const float* __restrict__ xvp,
+                                     float* __restrict__ xva, int64_t E,
+                                     int kw, int npanels) {
+  for (int64_t i = gidx(); i < E * 4; i += gstride()) {
+    const int64_t e = i >> 2;
+    const int q = (int)(i & 3);
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int p = 0; p < npanels; ++p) {
+      const float4 v = *reinterpret_cast<const float4*>(
+          &xvp[((int64_t)p * E + e) * 16 + 4 * q]);
+      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    *reinterpret_cast<float4*>(&xva[e * kw + 4 * q]) = s;
   }
 }
 
@@ -1116,6 +1257,20 @@ __global__ void db_reduce_kernel(const float* __restrict__ db_slab,
 // Bindings
 // ---------------------------------------------------------------------------
 
+// Stage-ring depth of gemm_fwd_glds_kernel for a given K — the one place
+// both gemm_fwd and gemm_env_step take it from.  Short-K GEMMs (few
+// stages) run the 2-deep ring — 24 KB LDS lets 6 blocks/CU co-reside and
+// prologue/drain is a large fraction of S (L2t K=64: 179 -> 157 us at
+// B=1M); long-K streams keep the 3-deep ring (L1t K=376: wash; ring 4
+// measured slower).  DPPO_FWD_RING=2/3/4 forces a depth.
+static int fwd_ring_for(int K) {
+  static const int ring_env = []() {
+    const char* e = getenv("DPPO_FWD_RING");
+    return e ? atoi(e) : 0;  // 0 = by shape
+  }();
+  return ring_env ? ring_env : (K <= 128 ? 2 : 3);
+}
+
 void gemm_fwd(torch::Tensor X, torch::Tensor Wt, torch::Tensor bias,
               int64_t activation, int64_t heads, torch::Tensor C,
               torch::Tensor v, torch::Tensor aux, int64_t wt_layout,
@@ -1193,15 +1348,7 @@ void gemm_fwd(torch::Tensor X, torch::Tensor Wt, torch::Tensor bias,
   const bool glds_ok = glds_env && !a.ablate && wt_layout == 0 &&
                        K % 4 == 0 && K >= 4 && N % 4 == 0 && N >= 4 &&
                        a.activation != 9999;
-  static const int ring_env = []() {
-    const char* e = getenv("DPPO_FWD_RING");
-    return e ? atoi(e) : 0;  // 0 = by shape (below); 2/3/4 force
-  }();
-  // by shape: short-K GEMMs (few stages) run the 2-deep ring — 24 KB
-  // LDS lets 6 blocks/CU co-reside and prologue/drain is a large
-  // fraction of S (L2t K=64: 179 -> 157 us at B=1M); long-K streams
-  // keep the 3-deep ring (L1t K=376: wash; ring 4 measured slower)
-  const int ring_sel = ring_env ? ring_env : (a.K <= 128 ? 2 : 3);
+  const int ring_sel = fwd_ring_for(a.K);
   #define DISPATCH_FWD(NTV, NPANEL)                                          \
     if (glds_ok && NTV == 2 && ring_sel == 2)                                \
       hipLaunchKernelGGL(gemm_fwd_glds_kernel<2>,                            \
@@ -1249,7 +1396,9 @@ void gemm_env_step(torch::Tensor xva, torch::Tensor M, torch::Tensor xin,
                    torch::Tensor epr,
                    torch::Tensor rewards, torch::Tensor dones,
                    torch::Tensor rsum, torch::Tensor seed_dev, double sigma,
-                   int64_t step) {
+                   int64_t step, torch::Tensor V, torch::Tensor xvp) {
+  // V / xvp non-empty: also fold the next step's x@V into the epilogue
+  // (per-panel partials -> xvp, summed into xva[:, 0:16] afterwards)
   const int64_t E = xva.size(0);
   const int K = static_cast<int>(xva.size(1));
   const int D = static_cast<int>(M.size(1));
@@ -1278,17 +1427,43 @@ void gemm_env_step(torch::Tensor xva, torch::Tensor M, torch::Tensor xin,
   a.env_rsum = rsum.data_ptr<float>();
   a.sigma = (float)sigma;
   a.step = (int)step;
+  const int panels = (D + 63) / 64;
+  const bool fold = xvp.numel() > 0;
+  if (fold) {
+    TORCH_CHECK(V.is_contiguous() && V.dim() == 2 && V.size(0) == D &&
+                    V.size(1) == 16,
+                "x@V fold needs V = [D][16]");
+    TORCH_CHECK(K >= 16 && xvp.is_contiguous() &&
+                xvp.numel() >= (int64_t)panels * E * 16);
+    a.env_V = V.data_ptr<float>();
+    a.env_xvp = xvp.data_ptr<float>();
+  }
   hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
   const int64_t tiles = (E + FWD_M - 1) / FWD_M;
-  const int panels = (D + 63) / 64;
-  hipLaunchKernelGGL(gemm_fwd_glds_kernel<3>,
-                     dim3((unsigned)tiles, (unsigned)panels),
-                     dim3(FWD_WAVES * 64), 0, stream, a);
+  const dim3 grid((unsigned)tiles, (unsigned)panels);
+  switch (fwd_ring_for(K)) {
+    case 2:
+      hipLaunchKernelGGL((gemm_fwd_glds_kernel<2, true>), grid,
+                         dim3(FWD_WAVES * 64), 0, stream, a);
+      break;
+    case 4:
+      hipLaunchKernelGGL((gemm_fwd_glds_kernel<4, true>), grid,
+                         dim3(FWD_WAVES * 64), 0, stream, a);
+      break;
+    default:
+      hipLaunchKernelGGL((gemm_fwd_glds_kernel<3, true>), grid,
+                         dim3(FWD_WAVES * 64), 0, stream, a);
+  }
   hipLaunchKernelGGL(env_finish2_kernel, dim3(elementwise_grid(E, 256)),
                      dim3(256), 0, stream, rsum.data_ptr<float>(),
                      t.data_ptr<int>(), horizons.data_ptr<int>(),
                      epr.data_ptr<float>(), rewards.data_ptr<float>(),
                      dones.data_ptr<float>(), E, D, panels);
+  if (fold)
+    hipLaunchKernelGGL(env_xv_reduce_kernel,
+                       dim3(elementwise_grid(E * 4, 256)), dim3(256), 0,
+                       stream, xvp.data_ptr<float>(), xva.data_ptr<float>(),
+                       E, K, panels);
 }
 
 // Grow-only scratch cache for the dW split slabs.  Allocating them per

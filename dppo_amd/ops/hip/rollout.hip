@@ -672,29 +672,49 @@ __global__ void env_finish_kernel(
   // seed on its own; nothing requires the two paths to share trajectories.
   constexpr int CMAX = (MAX_D / 4 + WAVE - 1) / WAVE;  // float4 chunks/lane
   const int nc4 = D / 4;
+  // Reward sum in the fused env epilogue's order (mfma_gemm.hip), so the
+  // two paths agree bitwise: per float4 chunk sq4(), the 16 chunks of one
+  // 64-column panel by an xor tree (chunk c = lane + 64*it is position
+  // lane%16 of panel lane/16 + 4*it), then the panels in ascending order.
   float4 xn[CMAX];
-  float ss = 0.f;
-  int it = 0;
-  for (int c = lane; c < nc4; c += WAVE, ++it) {
-    const int d = 4 * c;
-    const float4 xv = *reinterpret_cast<const float4*>(&xin[e * D + d]);
-    const float4 gv = *reinterpret_cast<const float4*>(&G[e * D + d]);
-    const float4 dv = *reinterpret_cast<const float4*>(&envd[d]);
-    float nz[4] = {0.f, 0.f, 0.f, 0.f};
-    if (sigma != 0.f) {
-      const float2 p0 = rng_normal2(seed, (int)e, step, 1000 + 2 * c);
-      const float2 p1 = rng_normal2(seed, (int)e, step, 1000 + 2 * c + 1);
-      nz[0] = p0.x; nz[1] = p0.y; nz[2] = p1.x; nz[3] = p1.y;
+  float pp[CMAX];
+  #pragma unroll
+  for (int it = 0; it < CMAX; ++it) {
+    const int c = lane + it * WAVE;
+    float ps = 0.f;
+    if (c < nc4) {
+      const int d = 4 * c;
+      const float4 xv = *reinterpret_cast<const float4*>(&xin[e * D + d]);
+      const float4 gv = *reinterpret_cast<const float4*>(&G[e * D + d]);
+      const float4 dv = *reinterpret_cast<const float4*>(&envd[d]);
+      float nz[4] = {0.f, 0.f, 0.f, 0.f};
+      if (sigma != 0.f) {
+        const float2 p0 = rng_normal2(seed, (int)e, step, 1000 + 2 * c);
+        const float2 p1 = rng_normal2(seed, (int)e, step, 1000 + 2 * c + 1);
+        nz[0] = p0.x; nz[1] = p0.y; nz[2] = p1.x; nz[3] = p1.y;
+      }
+      float4 v;
+      v.x = fast_tanhf(xv.x * dv.x + gv.x + sigma * nz[0]);
+      v.y = fast_tanhf(xv.y * dv.y + gv.y + sigma * nz[1]);
+      v.z = fast_tanhf(xv.z * dv.z + gv.z + sigma * nz[2]);
+      v.w = fast_tanhf(xv.w * dv.w + gv.w + sigma * nz[3]);
+      xn[it] = v;
+      ps = sq4(v);
     }
-    float4 v;
-    v.x = fast_tanhf(xv.x * dv.x + gv.x + sigma * nz[0]);
-    v.y = fast_tanhf(xv.y * dv.y + gv.y + sigma * nz[1]);
-    v.z = fast_tanhf(xv.z * dv.z + gv.z + sigma * nz[2]);
-    v.w = fast_tanhf(xv.w * dv.w + gv.w + sigma * nz[3]);
-    xn[it] = v;
-    ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    #pragma unroll
+    for (int off = 8; off > 0; off >>= 1) ps += __shfl_xor(ps, off, 16);
+    pp[it] = ps;
   }
-  ss = wave_reduce_sum(ss);
+  float ss = 0.f;
+  const int npanels = (D + 63) / 64;
+  #pragma unroll
+  for (int it = 0; it < CMAX; ++it) {
+    #pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float part = __shfl(pp[it], g * 16, WAVE);
+      if (4 * it + g < npanels) ss += part;
+    }
+  }
   int done;
   if (lane == 0) {
     const float r = 1.0f - ss / D;
@@ -711,8 +731,10 @@ __global__ void env_finish_kernel(
     t[e] = tc;
   }
   done = __shfl(done, 0, WAVE);
-  it = 0;
-  for (int c = lane; c < nc4; c += WAVE, ++it) {
+  #pragma unroll
+  for (int it = 0; it < CMAX; ++it) {
+    const int c = lane + it * WAVE;
+    if (c >= nc4) break;
     const int d = 4 * c;
     float4 v = xn[it];
     if (done) {

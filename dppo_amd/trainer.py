@@ -502,6 +502,10 @@ class DPPOEngine:
             eps_dev=torch.zeros(1, dtype=torch.float32, device=dev),
             epr_before=torch.empty(E, device=dev),
             rsum=torch.zeros(((D + 63) // 64) * E, device=dev),
+            # per-panel next-state @ V partials of the x@V fold (the fold
+            # kernel is written for rank 16; other ranks keep the GEMM)
+            xvp=(torch.empty(((D + 63) // 64) * E * 16, device=dev)
+                 if r == 16 else None),
             empty=torch.empty(0, device=dev),
             # whole-batch activation blob in the update path's acts layout
             # ([B*H1 | B*H2 | ...]): the rollout's layer GEMMs write here
@@ -514,7 +518,20 @@ class DPPOEngine:
 
     @staticmethod
     def _env_fused() -> bool:
-        return os.environ.get("DPPO_ENV_FUSED") == "1"
+        """Env transition in the G-GEMM epilogue (default);
+        DPPO_ENV_FUSED=0 restores the split G-GEMM + env_finish path."""
+        return os.environ.get("DPPO_ENV_FUSED", "1") != "0"
+
+    @staticmethod
+    def _xv_fold() -> bool:
+        """DPPO_XV_FOLD=1: the fused env epilogue also computes the next
+        step's x@V from the state tile it just finished (needs the fused
+        env path).  Measured +2% at the flagship, but the reassociated
+        x@V perturbs the states themselves, and after two training rounds
+        the parameters sit further from the split path's than the accepted
+        reward-reassociation noise (profiles/r03_rollout_env_fused.txt) —
+        opt-in."""
+        return os.environ.get("DPPO_XV_FOLD", "0") == "1"
 
     def _v3_body(self, states, pdflats, actions, values, rewards, dones,
                  boot_v):
@@ -555,6 +572,9 @@ class DPPOEngine:
         for hh in hs:
             acts_views.append(v3["acts"].narrow(0, off, B * hh).view(B, hh))
             off += B * hh
+        fused = self._env_fused()
+        fold = fused and self._xv_fold() and v3["xvp"] is not None
+        no_fold = (v3["empty"], v3["empty"])
         for st in range(T):
             xin = states[st]
             h = xin
@@ -570,9 +590,11 @@ class DPPOEngine:
             else:
                 ext.gemm_fwd(h, wh, bh, 2, 1, pdflats[st], values[st],
                              pdflats[st], 1, 0, 0)
-            # XV = x @ V into the concat buffer's first rank columns
-            ext.gemm_fwd(xin, v3["V"], v3["bz_r"], 2, 0, v3["xva"],
-                         v3["xva"], v3["xva"], 0, 0, v3["kw"])
+            # XV = x @ V into the concat buffer's first rank columns; with
+            # the fold, step st-1's env epilogue already left it there
+            if not fold or st == 0:
+                ext.gemm_fwd(xin, v3["V"], v3["bz_r"], 2, 0, v3["xva"],
+                             v3["xva"], v3["xva"], 0, 0, v3["kw"])
             ext.rollout_sample(pdflats[st], actions[st], v3["xva"],
                                v3["seed_dev"], v3["eps_dev"], st,
                                v3["va_off"], low, high)
@@ -582,17 +604,20 @@ class DPPOEngine:
             # the next round's states[0]: one [E][D] stream per step, no
             # mirror write
             xout = states[st + 1] if st + 1 < T else env.x
-            if self._env_fused():
+            if fused:
                 # G = [XV|act] @ [U;B] with the env transition fused into
-                # the GEMM epilogue (identical math and RNG slots).  Saves
-                # the [E][D] G round trip but pays per-ELEMENT Box-Muller
-                # (the separate env_finish shares one hash per dim pair):
-                # measured net -4ms/round at the flagship config, so the
-                # split path stays the default (DPPO_ENV_FUSED=1 opts in).
+                # the GEMM epilogue: the accumulators are repacked through
+                # LDS into env_finish's float4 layout (same math, RNG slots
+                # and per-element work; states bitwise equal to the split
+                # path), so the [E][D] G write + read never happen.  With
+                # the fold the same epilogue also leaves the next step's
+                # x@V in xva.
                 ext.gemm_env_step(v3["xva"], v3["M"], xin, xout, env.d,
                                   env.horizons_i32, env.t, self.epr,
                                   rewards[st], dones[st], v3["rsum"],
-                                  v3["seed_dev"], float(env.NOISE), st)
+                                  v3["seed_dev"], float(env.NOISE), st,
+                                  *((v3["V"], v3["xvp"]) if fold
+                                    else no_fold))
             else:
                 ext.gemm_fwd(v3["xva"], v3["M"], v3["bz_D"], 2, 0, v3["G"],
                              v3["G"], v3["G"], 0, 0, 0)
