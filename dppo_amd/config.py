@@ -174,6 +174,8 @@ class DPPOConfig:
 #: Others/distributions.py:231-243), so every family is trainable here
 GAME_SHAPES: Dict[str, Tuple[int, str, object]] = {
     "CartPole-v0": (4, "discrete", 2),
+    "Acrobot-v1": (6, "discrete", 3),
+    "LunarLander-v2": (8, "discrete", 4),
     "Pendulum-v1": (3, "box", 1),
     "HalfCheetah-v4": (17, "box", 6),
     "Humanoid-v4": (376, "box", 17),

@@ -124,6 +124,15 @@ std::vector<torch::Tensor> rollout_run(
     int64_t T, int64_t act_dim, int64_t seed, torch::Tensor out_buf,
     int64_t ablate);
 
+std::vector<torch::Tensor> rollout_run_cat(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation,
+    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
+    double noise, double eps_explore,
+    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
+    int64_t T, int64_t n_actions, int64_t seed, torch::Tensor out_buf,
+    int64_t ablate);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gae_scan", &gae_scan,
           "segmented GAE reverse scan + whitening (gfx950)");
@@ -151,6 +160,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "graph-replayable fused Adam (device step/lr) (gfx950)");
   mod.def("rollout_run", &rollout_run,
           "fused T-step rollout: MLP fwd + sample + synthetic env (gfx950)");
+  mod.def("rollout_run_cat", &rollout_run_cat,
+          "fused T-step rollout, Discrete/Categorical policy: MLP fwd + "
+          "Gumbel-max sample + synthetic env, int64 actions (gfx950)");
   mod.def("rollout_sample", &rollout_sample,
           "per-step action sampling + eps-greedy (v3 rollout) (gfx950)");
   mod.def("gemm_env_step", &gemm_env_step,

@@ -35,8 +35,10 @@
 //     23-pointer struct spilled 80 SGPRs to VGPR lanes.
 //
 // Limits (checked in the binding): obs_dim <= 512, hidden <= 128,
-// <= 3 hidden layers, act_dim <= 32, rank <= 32, Box/DiagGaussian only.
-// The wide config (BASELINE #5) takes the GEMM path instead.
+// <= 3 hidden layers, rank <= 32; Box/DiagGaussian with act_dim <= 32, or
+// (FAM_CAT instantiations, rollout_run_cat) Discrete/Categorical with
+// 2 <= n_actions <= 64.  The wide config (BASELINE #5) takes the GEMM path
+// instead.
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -55,6 +57,13 @@ constexpr int MAX_HIDDEN = 3;
 
 constexpr int NWAVES = 4;  // waves per block
 
+// policy family of a rollout_kernel instantiation: the trunk, env phase and
+// bookkeeping are shared; heads width, sampler, epsilon overlay, the env's
+// action input and the action output differ.
+constexpr int FAM_BOX = 0;  // DiagGaussian: P = 2A pd params, float actions
+constexpr int FAM_CAT = 1;  // Categorical: P = K logits, int64 action index
+constexpr int MAX_K = 64;
+
 // The LDS image is dynamically sized to the ACTUAL dims (obs, widest
 // hidden, act): a MAX-dims static image (44 KB at the flagship shapes
 // needing only 27 KB) capped residency at 3 blocks/CU and left the
@@ -62,22 +71,27 @@ constexpr int NWAVES = 4;  // waves per block
 // LDS accesses stay 16-B aligned.
 struct LdsMap {
   int x, h0, h1, pd, act, xv, part, val, rsum, epr, racc;  // float offsets
-  int xs, hs, total;  // x row stride, h row stride, total floats
+  int xs, hs, ps, total;  // x / h / k-split partial row strides, total floats
 };
 
-DEV_INLINE LdsMap lds_map(int D, int Hmax, int A, int rank, int et) {
+// P: pd-param width, actw: action slab width, partw: widest row the k-split
+// partial slab holds.  Box: (2A, A, Hmax).  Categorical: (K, 1,
+// max(Hmax, K+1)) — its K+1 head columns may exceed the trunk width.
+DEV_INLINE LdsMap lds_map(int D, int Hmax, int P, int actw, int partw,
+                          int rank, int et) {
   auto r4 = [](int v) { return (v + 3) & ~3; };
   LdsMap m;
   m.xs = r4(D);
   m.hs = r4(Hmax);
+  m.ps = r4(partw);
   int o = 0;
   m.x = o; o += et * m.xs;
   m.h0 = o; o += et * m.hs;
   m.h1 = o; o += et * m.hs;
-  m.pd = o; o += et * r4(2 * A);
-  m.act = o; o += et * r4(A);
+  m.pd = o; o += et * r4(P);
+  m.act = o; o += et * r4(actw);
   m.xv = o; o += et * r4(rank);
-  m.part = o; o += NWAVES * et * m.hs;
+  m.part = o; o += NWAVES * et * m.ps;
   m.val = o; o += et;
   m.rsum = o; o += et;
   m.epr = o; o += et;
@@ -99,10 +113,12 @@ struct RolloutArgs {
   int* t;                // [E]
   float* epr;            // [E]
   float* out;            // states|pdflats|actions|values|rewards|dones|boot|moments
+                         // (FAM_CAT: actions(int64)|states|pdflats(logits)|
+                         // values|rewards|dones|boot|moments)
   int off_W[MAX_HIDDEN], off_b[MAX_HIDDEN];
   int dims[MAX_HIDDEN + 1];
   int off_Wv, off_bv, off_Wp, off_bp;
-  int n_hidden, act_dim, activation, rank, h_max;
+  int n_hidden, act_dim, activation, rank, h_max;  // FAM_CAT: act_dim = K
   float noise, act_low, act_high, eps_explore;
   int T, E, D;
   unsigned seed;
@@ -176,7 +192,8 @@ DEV_INLINE float u2f_mono(unsigned u) {
 // counts — the same instruction-count program as mlp_chunk_kernel;
 // profiles/r01_chunk_kernel_notes.md round-2 target list).
 template <int MINWAVES, int ET = ENV_TILE, int TD = 0, int TH = 0,
-          int TA = 0, int TNH = 0, int TRANK = 0, int TACT = 0>
+          int TA = 0, int TNH = 0, int TRANK = 0, int TACT = 0,
+          int FAM = FAM_BOX>
 __launch_bounds__(NWAVES * 64, MINWAVES)
 __global__ void rollout_kernel(RolloutArgs a) {
   const int tid = threadIdx.x;      // block = 4 waves of 64
@@ -188,7 +205,7 @@ __global__ void rollout_kernel(RolloutArgs a) {
   const int nE = TD ? ET : min(ET, a.E - e0);
   const int D = TD ? TD : a.D;
   const int A = TA ? TA : a.act_dim;
-  const int P = 2 * A;
+  const int P = (FAM == FAM_CAT) ? A : 2 * A;
   const int T = a.T, E = a.E;
   const int RNK = TRANK ? TRANK : a.rank;
   const int NHID = TNH ? TNH : a.n_hidden;
@@ -196,12 +213,18 @@ __global__ void rollout_kernel(RolloutArgs a) {
   const int ACT = TACT ? (TACT > 0 ? 1 : 0) : a.activation;
 
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const LdsMap lm = lds_map(D, HMAX, A, RNK, ET);
+  const LdsMap lm = (FAM == FAM_CAT)
+                        ? lds_map(D, HMAX, P, 1, max(HMAX, P + 1), RNK, ET)
+                        : lds_map(D, HMAX, P, A, HMAX, RNK, ET);
   const int X_OFF = lm.x, H0_OFF = lm.h0, H1_OFF = lm.h1, PD_OFF = lm.pd;
   const int ACT_OFF = lm.act, XV_OFF = lm.xv, PART_OFF = lm.part;
   const int MAX_D_S = lm.xs, MAX_H_S = lm.hs;
-  const int PD_S = ((2 * A) + 3) & ~3, ACT_S = (A + 3) & ~3,
+  const int PD_S = (P + 3) & ~3,
+            ACT_S = (FAM == FAM_CAT) ? 4 : (A + 3) & ~3,
             XV_S = (RNK + 3) & ~3;
+  // k-split partial row stride: the trunk width for Box (unchanged map);
+  // Categorical widens it to hold the K+1 head columns
+  const int PART_S = (FAM == FAM_CAT) ? lm.ps : MAX_H_S;
   float* val_lds = &lds[lm.val];
   float* rsum_lds = &lds[lm.rsum];
   float* epr_lds = &lds[lm.epr];
@@ -214,11 +237,14 @@ __global__ void rollout_kernel(RolloutArgs a) {
   const float* env_Vt = env_d + D;
   const float* env_U = env_Vt + (int64_t)RNK * D;
   const float* env_B = env_U + (int64_t)RNK * D;
-  // output blob offsets
-  float* out_states = a.out;
+  // output blob offsets (Categorical: the int64 action indices lead the
+  // blob so they are 8-byte aligned; no float action region)
+  float* out_states =
+      a.out + ((FAM == FAM_CAT) ? 2 * (int64_t)T * E : (int64_t)0);
   float* out_pdflats = out_states + (int64_t)T * E * D;
   float* out_actions = out_pdflats + (int64_t)T * E * P;
-  float* out_values = out_actions + (int64_t)T * E * A;
+  float* out_values =
+      out_actions + ((FAM == FAM_CAT) ? (int64_t)0 : (int64_t)T * E * A);
   float* out_rewards = out_values + (int64_t)T * E;
   float* out_dones = out_rewards + (int64_t)T * E;
   float* out_boot = out_dones + (int64_t)T * E;
@@ -232,6 +258,11 @@ __global__ void rollout_kernel(RolloutArgs a) {
   if (tid < nE) {
     epr_lds[tid] = a.epr[e0 + tid];
     tc_lds[tid] = a.t[e0 + tid];
+  }
+  if constexpr (FAM == FAM_CAT) {
+    // action indices address env B rows: keep every tile slot (tail envs,
+    // ablated sampling) a valid row
+    if (tid < ET) lds[ACT_OFF + tid * ACT_S] = __int_as_float(0);
   }
   __syncthreads();
 
@@ -278,7 +309,7 @@ __global__ void rollout_kernel(RolloutArgs a) {
       }
       #pragma unroll
       for (int e = 0; e < ET; ++e)
-        lds[PART_OFF + (wv * ET + e) * MAX_H_S + u] = acc[e];
+        lds[PART_OFF + (wv * ET + e) * PART_S + u] = acc[e];
     }
   };
 
@@ -341,7 +372,7 @@ __global__ void rollout_kernel(RolloutArgs a) {
         float sum = bias[u];
         #pragma unroll
         for (int w = 0; w < NWAVES; ++w)
-          sum += lds[PART_OFF + (w * ET + e) * MAX_H_S + u];
+          sum += lds[PART_OFF + (w * ET + e) * PART_S + u];
         lds[out_off + e * MAX_H_S + u] =
             ACT ? fast_tanhf(sum) : fmaxf(sum, 0.f);
       }
@@ -366,7 +397,7 @@ __global__ void rollout_kernel(RolloutArgs a) {
         float sum = a.params[(u == P) ? a.off_bv : a.off_bp + u];
         #pragma unroll
         for (int w = 0; w < NWAVES; ++w)
-          sum += lds[PART_OFF + (w * ET + e) * MAX_H_S + u];
+          sum += lds[PART_OFF + (w * ET + e) * PART_S + u];
         if (u == P) val_lds[e] = sum;
         else lds[PD_OFF + e * PD_S + u] = sum;
       }
@@ -374,7 +405,45 @@ __global__ void rollout_kernel(RolloutArgs a) {
     }
 
     // ---- sample actions (threads = (env, dim) pairs) ----
-    if (!(a.ablate & 4)) {
+    if constexpr (FAM == FAM_CAT) {
+      // Gumbel-max, argmax_j(logit_j - log(-log u_j)): wave wv takes envs
+      // wv, wv+4; lane j draws class j, a butterfly argmax (ties -> lowest
+      // index) leaves the winner in every lane.  Every tile slot is
+      // sampled (tail slots hold finite bias-only logits), so the action
+      // slab always holds a valid env-B row.
+      if (!(a.ablate & 4)) {
+        for (int e = wv; e < ET; e += NWAVES) {
+          const int ge = e0 + e;
+          float best = -3.0e38f;
+          int arg = lane;
+          if (lane < A) {
+            // u in (0, 1] can round to exactly 1: floor -log u at 2^-24 so
+            // the Gumbel draw stays finite (never +inf, never NaN)
+            const float nl = fmaxf(-__logf(rng_uniform(a.seed, ge, step, lane)),
+                                   5.9604645e-8f);
+            best = lds[PD_OFF + e * PD_S + lane] - __logf(nl);
+          }
+          #pragma unroll
+          for (int off = WAVE / 2; off > 0; off >>= 1) {
+            const float ob = __shfl_xor(best, off, WAVE);
+            const int oa = __shfl_xor(arg, off, WAVE);
+            if (ob > best || (ob == best && oa < arg)) {
+              best = ob;
+              arg = oa;
+            }
+          }
+          // epsilon-greedy overlay (Worker.py:149-152): uniform index
+          const float u_dec = rng_uniform(a.seed, ge, step, 90001);
+          if (u_dec < a.eps_explore) {
+            const float u = rng_uniform(a.seed, ge, step, 90010);
+            arg = (int)(u * A);
+          }
+          // clamp: u == 1 gives K; non-finite logits must not index past B
+          arg = max(0, min(A - 1, arg));
+          if (lane == 0) lds[ACT_OFF + e * ACT_S] = __int_as_float(arg);
+        }
+      }
+    } else if (!(a.ablate & 4)) {
       const int e = tid / MAX_A;   // 8 groups x 32 dims
       const int j = tid % MAX_A;
       if (e < nE && j < A) {
@@ -401,7 +470,15 @@ __global__ void rollout_kernel(RolloutArgs a) {
       for (int e = 0; e < nE; ++e) {
         const int64_t row = (int64_t)step * E + e0 + e;
         if (tid < P) out_pdflats[row * P + tid] = lds[PD_OFF + e * PD_S + tid];
-        if (tid < A) out_actions[row * A + tid] = lds[ACT_OFF + e * ACT_S + tid];
+        if constexpr (FAM == FAM_BOX) {
+          if (tid < A)
+            out_actions[row * A + tid] = lds[ACT_OFF + e * ACT_S + tid];
+        }
+      }
+      if constexpr (FAM == FAM_CAT) {
+        if (tid < nE)
+          reinterpret_cast<int64_t*>(a.out)[(int64_t)step * E + e0 + tid] =
+              __float_as_int(lds[ACT_OFF + tid * ACT_S]);
       }
       if (tid < nE) out_values[(int64_t)step * E + e0 + tid] = val_lds[tid];
     }
@@ -453,6 +530,14 @@ __global__ void rollout_kernel(RolloutArgs a) {
           for (int e = 0; e < ET; ++e)
             low[e] += lds[XV_OFF + e * XV_S + rr] * uv;
         }
+        if constexpr (FAM == FAM_CAT) {
+          // a_in = B[a_e][:]: one coalesced row gather per env (lane == d),
+          // the eager index_select exactly
+          #pragma unroll
+          for (int e = 0; e < ET; ++e)
+            ain[e] = env_B[(int64_t)__float_as_int(lds[ACT_OFF + e * ACT_S]) *
+                               D + d];
+        } else {  // Box: a_in = act @ B (body kept at the outer indent)
         int j = 0;
         for (; j + 4 <= A; j += 4) {
           const float b0 = env_B[(int64_t)(j + 0) * D + d];
@@ -472,6 +557,7 @@ __global__ void rollout_kernel(RolloutArgs a) {
           #pragma unroll
           for (int e = 0; e < ET; ++e)
             ain[e] += lds[ACT_OFF + e * ACT_S + j] * bvv;
+        }
         }
       }
       for (int e = 0; e < nE; ++e) {
@@ -532,7 +618,7 @@ __global__ void rollout_kernel(RolloutArgs a) {
         float sum = bias[u];
         #pragma unroll
         for (int w = 0; w < NWAVES; ++w)
-          sum += lds[PART_OFF + (w * ET + e) * MAX_H_S + u];
+          sum += lds[PART_OFF + (w * ET + e) * PART_S + u];
         lds[out_off + e * MAX_H_S + u] =
             ACT ? fast_tanhf(sum) : fmaxf(sum, 0.f);
       }
@@ -749,14 +835,16 @@ __global__ void env_finish_kernel(
 
 }  // namespace
 
-std::vector<torch::Tensor> rollout_run(
-    torch::Tensor params, std::vector<int64_t> offsets,
-    std::vector<int64_t> dims, int64_t activation,
-    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
+// Argument checks and the RolloutArgs fill shared by both policy families
+// (act_dim is the Box action dim or the Categorical class count; the
+// family-specific bound on it is checked by the caller).
+static RolloutArgs rollout_args(
+    const torch::Tensor& params, const std::vector<int64_t>& offsets,
+    const std::vector<int64_t>& dims, int64_t activation,
+    const torch::Tensor& envblob, int64_t rank, const torch::Tensor& horizons,
     double noise, double act_low, double act_high, double eps_explore,
-    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
-    int64_t T, int64_t act_dim, int64_t seed, torch::Tensor out_buf,
-    int64_t ablate) {
+    const torch::Tensor& x, const torch::Tensor& t, const torch::Tensor& epr,
+    int64_t T, int64_t act_dim, int64_t seed, int64_t ablate) {
   // offsets: [W0, b0, W1, b1, ..., Wv, bv, Wp, bp] into params
   // dims: [obs, h1, ..., hN]
   const int64_t E = x.size(0);
@@ -766,8 +854,7 @@ std::vector<torch::Tensor> rollout_run(
   TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kFloat32 && x.is_contiguous());
   TORCH_CHECK(params.is_contiguous() && params.dtype() == torch::kFloat32);
   TORCH_CHECK(n_hidden >= 1 && n_hidden <= MAX_HIDDEN, "1..3 hidden layers");
-  TORCH_CHECK(D <= MAX_D && A <= MAX_A && rank <= MAX_R,
-              "dims exceed rollout-kernel limits");
+  TORCH_CHECK(D <= MAX_D && rank <= MAX_R, "dims exceed rollout-kernel limits");
   TORCH_CHECK(dims[0] == D, "first layer must consume obs_dim");
   TORCH_CHECK(horizons.dtype() == torch::kInt32 && t.dtype() == torch::kInt32);
   TORCH_CHECK(static_cast<int>(offsets.size()) == 2 * n_hidden + 4);
@@ -808,6 +895,35 @@ std::vector<torch::Tensor> rollout_run(
   a.D = static_cast<int>(D);
   a.seed = static_cast<unsigned>(seed & 0xFFFFFFFFULL);
   a.ablate = static_cast<int>(ablate);
+  return a;
+}
+
+// DPPO_ROLLOUT_MW: absent -> -1 (auto); see rollout_run
+static int rollout_mw_env() {
+  static const int mw_env = []() {
+    const char* e = getenv("DPPO_ROLLOUT_MW");
+    return e ? atoi(e) : -1;  // -1 = unset, distinct from explicit 0
+  }();
+  return mw_env;
+}
+
+std::vector<torch::Tensor> rollout_run(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation,
+    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
+    double noise, double act_low, double act_high, double eps_explore,
+    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
+    int64_t T, int64_t act_dim, int64_t seed, torch::Tensor out_buf,
+    int64_t ablate) {
+  const int64_t E = x.size(0);
+  const int64_t D = x.size(1);
+  const int A = static_cast<int>(act_dim);
+  TORCH_CHECK(A <= MAX_A, "dims exceed rollout-kernel limits");
+  RolloutArgs a = rollout_args(params, offsets, dims, activation, envblob,
+                               rank, horizons, noise, act_low, act_high,
+                               eps_explore, x, t, epr, T, act_dim, seed,
+                               ablate);
+  const int h_max = a.h_max;
 
   const int P = 2 * A;
   const int64_t n_out = T * E * (D + P + A + 3) + E + 5;
@@ -842,10 +958,7 @@ std::vector<torch::Tensor> rollout_run(
   // 1-wave/SIMD minimum, big grids the 4-wave one); explicit values pick
   // the __launch_bounds__ min-waves instantiation: >=4 -> <4>, 2..3 ->
   // <3>, 0..1 -> <1> (0 = "no minimum" = the 128-VGPR-cap-lifted kernel).
-  static const int mw_env = []() {
-    const char* e = getenv("DPPO_ROLLOUT_MW");
-    return e ? atoi(e) : -1;  // -1 = unset, distinct from explicit 0
-  }();
+  const int mw_env = rollout_mw_env();
   const int mw = mw_env >= 0 ? mw_env : (grid <= N_CU ? 1 : 4);
   // exact-shape specializations for the BASELINE families (index maps,
   // trip counts and the LDS map constant-folded)
@@ -915,6 +1028,115 @@ std::vector<torch::Tensor> rollout_run(
   auto states = take({T, E, D});
   auto pdflats = take({T, E, (int64_t)P});
   auto actions = take({T, E, (int64_t)A});
+  auto values = take({T, E});
+  auto rewards = take({T, E});
+  auto dones = take({T, E});
+  auto boot_v = take({E});
+  auto moments = take({5});
+  moments.zero_();
+
+  hipLaunchKernelGGL(ep_moments_kernel,
+                     dim3(static_cast<int>((E + 255) / 256)), dim3(256), 0,
+                     stream, rewards.data_ptr<float>(), dones.data_ptr<float>(),
+                     epr_in.data_ptr<float>(), moments.data_ptr<float>(), T, E);
+  hipLaunchKernelGGL(ep_moments_decode_kernel, dim3(1), dim3(1), 0, stream,
+                     moments.data_ptr<float>());
+  return {states, pdflats, actions, values, rewards, dones, boot_v, moments};
+}
+
+// Discrete/Categorical whole-rollout: the FAM_CAT instantiations of
+// rollout_kernel (K logits + value heads, Gumbel-max sampling, uniform-index
+// epsilon overlay, a_in = B[a] row gather, int64 action indices written by
+// the kernel).  Launch selection follows rollout_run; runtime shapes only.
+std::vector<torch::Tensor> rollout_run_cat(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation,
+    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
+    double noise, double eps_explore,
+    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
+    int64_t T, int64_t n_actions, int64_t seed, torch::Tensor out_buf,
+    int64_t ablate) {
+  const int64_t E = x.size(0);
+  const int64_t D = x.size(1);
+  const int K = static_cast<int>(n_actions);
+  TORCH_CHECK(n_actions >= 2 && n_actions <= MAX_K,
+              "categorical rollout supports 2 <= K <= 64");
+  RolloutArgs a = rollout_args(params, offsets, dims, activation, envblob,
+                               rank, horizons, noise, 0.0, 0.0, eps_explore,
+                               x, t, epr, T, n_actions, seed, ablate);
+  const int h_max = a.h_max;
+  TORCH_CHECK(envblob.is_cuda() && envblob.is_contiguous() &&
+                  envblob.dtype() == torch::kFloat32 &&
+                  envblob.numel() == D + 2 * rank * D + (int64_t)K * D,
+              "env blob must be d | Vt[r][D] | U[r][D] | B[K][D]");
+  TORCH_CHECK(horizons.numel() == E && t.numel() == E && epr.numel() == E);
+  TORCH_CHECK(params.numel() >=
+                  offsets[2 * a.n_hidden + 2] + (int64_t)dims.back() * K &&
+                  params.numel() >= offsets[2 * a.n_hidden + 3] + K,
+              "weight blob too small for the K-wide policy head");
+
+  // blob: actions(int64)[T*E] | states | logits | values | rewards | dones |
+  // boot | moments, in floats (the int64 region is 2*T*E floats wide and
+  // leads the blob so it is 8-byte aligned)
+  const int64_t n_out = T * E * (2 + D + K + 3) + E + 5;
+  torch::Tensor out = (out_buf.numel() == n_out)
+                          ? out_buf
+                          : torch::empty({n_out}, x.options());
+  TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kFloat32 &&
+              out.is_contiguous());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr<float>()) % 8 == 0,
+              "rollout output blob must be 8-byte aligned");
+  auto epr_in = epr.clone();
+  a.out = out.data_ptr<float>();
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  const int et = ((E + ENV_TILE - 1) / ENV_TILE < 128 && E % 2 == 0) ? 2
+                                                                     : ENV_TILE;
+  const int grid = static_cast<int>((E + et - 1) / et);
+  auto r4 = [](int v) { return (v + 3) & ~3; };
+  // mirrors the FAM_CAT lds_map: the k-split partial rows are sized for
+  // the K+1 head columns when those exceed the trunk width
+  const size_t lds_bytes =
+      (et * (r4((int)D) + 2 * r4(h_max) + r4(K) + r4(1) + r4((int)rank) + 4) +
+       NWAVES * et * r4(std::max(h_max, K + 1))) *
+      sizeof(float);
+  const int mw_env = rollout_mw_env();
+  const int mw = mw_env >= 0 ? mw_env : (grid <= N_CU ? 1 : 4);
+  const dim3 g(grid), b(NWAVES * WAVE);
+  if (mw >= 4) {
+    if (et == 2)
+      hipLaunchKernelGGL((rollout_kernel<4, 2, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
+                         b, lds_bytes, stream, a);
+    else
+      hipLaunchKernelGGL((rollout_kernel<4, 8, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
+                         b, lds_bytes, stream, a);
+  } else if (mw >= 2) {
+    if (et == 2)
+      hipLaunchKernelGGL((rollout_kernel<3, 2, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
+                         b, lds_bytes, stream, a);
+    else
+      hipLaunchKernelGGL((rollout_kernel<3, 8, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
+                         b, lds_bytes, stream, a);
+  } else {
+    if (et == 2)
+      hipLaunchKernelGGL((rollout_kernel<1, 2, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
+                         b, lds_bytes, stream, a);
+    else
+      hipLaunchKernelGGL((rollout_kernel<1, 8, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
+                         b, lds_bytes, stream, a);
+  }
+
+  auto actions = out.narrow(0, 0, 2 * T * E).view(torch::kInt64).view({T, E});
+  int64_t o = 2 * T * E;
+  auto take = [&](std::vector<int64_t> shape) {
+    int64_t n = 1;
+    for (auto sdim : shape) n *= sdim;
+    auto v = out.narrow(0, o, n).view(shape);
+    o += n;
+    return v;
+  };
+  auto states = take({T, E, D});
+  auto pdflats = take({T, E, (int64_t)K});
   auto values = take({T, E});
   auto rewards = take({T, E});
   auto dones = take({T, E});
