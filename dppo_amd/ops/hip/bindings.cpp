@@ -115,6 +115,16 @@ void mlp_chunk_train(
     torch::Tensor lr_dev, torch::Tensor coef, torch::Tensor flat_grad,
     bool fuse_adam, double beta1, double beta2, double eps);
 
+bool mlp_mid_supported(int64_t H1, int64_t H2, int64_t A, int64_t n_hidden);
+
+void mlp_mid_bwd(torch::Tensor params, std::vector<int64_t> offsets,
+                 torch::Tensor h1, torch::Tensor h2, torch::Tensor pdflat,
+                 torch::Tensor v, torch::Tensor oldflat, torch::Tensor oldv,
+                 torch::Tensor act, torch::Tensor adv, torch::Tensor etr,
+                 int64_t activation, torch::Tensor clip_dev, double clip,
+                 double entcoeff, double vcoeff, torch::Tensor dz1,
+                 torch::Tensor grad);
+
 std::vector<torch::Tensor> rollout_run(
     torch::Tensor params, std::vector<int64_t> offsets,
     std::vector<int64_t> dims, int64_t activation,
@@ -183,4 +193,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("mlp_chunk_train", &mlp_chunk_train,
           "fused small-MLP training chunk step: fwd+PPO grad+bwd+dW "
           "partials + slab-reduce Adam (gfx950)");
+  mod.def("mlp_mid_supported", &mlp_mid_supported,
+          "shape eligibility for the fused update-middle kernel (gfx950)");
+  mod.def("mlp_mid_bwd", &mlp_mid_bwd,
+          "fused update middle: PPO grad + heads/L2 dgrad + dW2/heads dW "
+          "partials -> dz1 and flat grad, no gh/dz2 in HBM (gfx950)");
 }

@@ -1547,6 +1547,13 @@ void dw_mfma(torch::Tensor delta, torch::Tensor acts, torch::Tensor grad_buf,
         std::min<int64_t>(split_cap, std::max<int64_t>(256, B / 4096)));
     a.splits = static_cast<int>(
         std::min<int64_t>(a.splits, std::max<int64_t>(1, B / DWG_K)));
+    {
+      // no empty trailing split: dw_glds_kernel returns early on one and
+      // leaves its slab rows unwritten for the reduce (B = 4099 with 256
+      // splits of 17 rows left 14 of them stale)
+      const int64_t rows_per = (B + a.splits - 1) / a.splits;
+      a.splits = static_cast<int>((B + rows_per - 1) / rows_per);
+    }
     auto& slab2 = dw_scratch(0, (int64_t)a.splits * out_dim * in_dim,
                              delta.options());
     auto& db_slab2 = dw_scratch(1, (int64_t)a.splits * out_dim,

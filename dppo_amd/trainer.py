@@ -1546,6 +1546,10 @@ class DPPOEngine:
         for hh in self.cfg.HIDDEN_SIZES:
             a_views.append(acts.narrow(0, off, B * hh).view(B, hh))
             off += B * hh
+        if self._mid_fused_mode():
+            # the mid kernel reads the head weights from the flat buffer
+            self._Wh_pad = None
+            return acts, a_views, batch.oldv, batch.oldflat
         with torch.no_grad():
             Wh_cat = torch.cat(
                 [self.pi.pi.weight, self.pi.vf.weight], dim=0).contiguous()
@@ -1586,11 +1590,14 @@ class DPPOEngine:
                 [self.pi.pi.weight, self.pi.vf.weight], dim=0
             ).contiguous()  # [P+1][HL]: heads fwd (layout 1)
             # dgrad Wt padded to gh's float4 row stride (zero rows: the
-            # gh pad columns multiply them and contribute nothing)
-            ldp = (Wh_cat.shape[0] + 3) & ~3
-            Wh_pad = torch.zeros(ldp, Wh_cat.shape[1],
-                                 device=Wh_cat.device)
-            Wh_pad[:Wh_cat.shape[0]] = Wh_cat
+            # gh pad columns multiply them and contribute nothing); the
+            # mid kernel reads the head weights from the flat buffer
+            Wh_pad = None
+            if not self._mid_fused_mode():
+                ldp = (Wh_cat.shape[0] + 3) & ~3
+                Wh_pad = torch.zeros(ldp, Wh_cat.shape[1],
+                                     device=Wh_cat.device)
+                Wh_pad[:Wh_cat.shape[0]] = Wh_cat
             bh = torch.cat([self.pi.pi.bias, self.pi.vf.bias]).contiguous()
         total = sum(B * dims[l + 1] for l in range(n_hidden))
         acts = torch.empty(total, device=states.device, dtype=states.dtype)
@@ -1621,13 +1628,74 @@ class DPPOEngine:
         self._Wh_pad = Wh_pad
         return acts, a_views, v, pdflat
 
+    # the DPPO_MID_FUSED default: what profiles/r05_update_mid_fused.txt
+    # measured fastest
+    MID_FUSED_DEFAULT = "load"
+
+    def _mid_fused_mode(self) -> str:
+        """DPPO_MID_FUSED=0|load: '' keeps the per-layer backward chain;
+        'load' runs the fused update-middle kernel (mlp_mid.hip) where the
+        shape is eligible.  Anything else is an error, not a fall-back.
+        Resolved once per engine and value of the variable."""
+        env = os.environ.get("DPPO_MID_FUSED", self.MID_FUSED_DEFAULT)
+        cached = getattr(self, "_mid_mode_cache", None)
+        if cached is not None and cached[0] == env:
+            return cached[1]
+        mode = self._resolve_mid_mode(env)
+        self._mid_mode_cache = (env, mode)
+        return mode
+
+    def _resolve_mid_mode(self, mode: str) -> str:
+        from .ops import hip_ext
+
+        if mode == "0":
+            return ""
+        if mode != "load":
+            raise ValueError(
+                f"DPPO_MID_FUSED={mode!r}: expected '0' or 'load'")
+        c = self.cfg
+        if self._act_kind != "box" or c.DTYPE != "float32":
+            return ""
+        if c.ACTIVATION not in ("tanh", "relu"):
+            return ""
+        hs = tuple(c.HIDDEN_SIZES)
+        if len(hs) != 2 or not hip_ext().mlp_mid_supported(
+                hs[0], hs[1], self.act_space.shape[0], len(hs)):
+            return ""
+        return mode
+
+    def _mid_backward(self, states, a_views, v, pdflat, oldflat, oldv,
+                      actions, adv, etr, clip: float) -> torch.Tensor:
+        """Fused middle of the backward: (h1, h2, pdflat, v, loss inputs)
+        -> dz1 plus the W2/b2/heads gradients in one kernel (gh and dz2
+        stay on-chip), then dW1/db1 from dz1.  Returns dz1."""
+        from .ops import hip_ext
+
+        ext = hip_ext()
+        c = self.cfg
+        offsets = [sl.start for sl in self.flat_pi.slices]
+        grad = self.flat_pi.flat_grad
+        dz1 = torch.empty_like(a_views[0])
+        ext.mlp_mid_bwd(
+            self.flat_pi.flat_param.detach(), offsets, a_views[0], a_views[1],
+            pdflat, v, oldflat, oldv, actions, adv, etr,
+            1 if c.ACTIVATION == "tanh" else 0, self._clip_dev_or_empty(),
+            clip, c.ENTCOEFF, c.VCOEFF, dz1, grad)
+        ext.dw_mfma(dz1, states, grad, offsets[0], offsets[1], -1, -1, -1, 0)
+        return dz1
+
     def _fused_backward(self, states, acts, a_views, v, pdflat,
                         oldflat, oldv, actions, adv, etr, clip: float) -> None:
         """GEMM-shaped backward into the (already zeroed) flat grad:
         wave-per-row loss grads -> dgrad GEMM chain (torch weight layouts
-        ARE the needed Wt; no transposes) -> split-K dW scatter."""
+        ARE the needed Wt; no transposes) -> split-K dW scatter.  Eligible
+        two-hidden-layer shapes take the fused middle kernel instead."""
         from .ops import hip_ext
 
+        if self._mid_fused_mode():
+            self._mid_backward(states, a_views, v, pdflat, oldflat, oldv,
+                               actions, adv, etr, clip)
+            return
         ext = hip_ext()
         c = self.cfg
         offsets = [sl.start for sl in self.flat_pi.slices]
