@@ -77,6 +77,16 @@ void gemm_fwd(torch::Tensor X, torch::Tensor Wt, torch::Tensor bias,
               torch::Tensor v, torch::Tensor aux, int64_t wt_layout,
               int64_t ablate, int64_t ldc);
 
+bool mlp_fwd_fused_supported(int64_t D, int64_t H1, int64_t H2, int64_t A);
+
+void mlp_fwd_fused(torch::Tensor X, torch::Tensor W1t, torch::Tensor b1,
+                   torch::Tensor W2t, torch::Tensor b2, torch::Tensor WhT_pad,
+                   torch::Tensor bh_pad, int64_t act_code, torch::Tensor h1,
+                   torch::Tensor h2, torch::Tensor pdflat, torch::Tensor v,
+                   torch::Tensor actions, torch::Tensor xva,
+                   torch::Tensor seed_dev, torch::Tensor eps_dev, int64_t step,
+                   int64_t va_off, double act_low, double act_high);
+
 void dw_mfma(torch::Tensor delta, torch::Tensor acts, torch::Tensor grad_buf,
              int64_t w_off, int64_t b_off, int64_t split_row, int64_t w_off2,
              int64_t b_off2, int64_t ablate);
@@ -186,6 +196,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "wave-per-row PPO loss gradient -> [g_pd | g_v] (gfx950)");
   mod.def("gemm_fwd", &gemm_fwd,
           "MFMA f32 layer forward C=act(X@Wt+b), fused tanh (gfx950)");
+  mod.def("mlp_fwd_fused_supported", &mlp_fwd_fused_supported,
+          "shape eligibility for the fused policy forward (gfx950)");
+  mod.def("mlp_fwd_fused", &mlp_fwd_fused,
+          "fused policy forward: L1 + L2 + heads (+ action sampling) in one "
+          "launch, h1/h2 written once and never re-read (gfx950)");
   mod.def("dw_mfma", &dw_mfma,
           "MFMA f32 split-K dW += delta^T@acts into flat grad (gfx950)");
   mod.def("mlp_chunk_supported", &mlp_chunk_supported,

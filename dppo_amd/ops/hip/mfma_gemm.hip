@@ -13,6 +13,10 @@
 //               L2 coalesced (reused by every row block).
 //   heads mode: same, N = 2A+1, no activation; epilogue splits columns
 //               into pdflat[B,2A] and v[B].
+//   mlp_fwd_fused: L1 -> L2 -> heads (-> action sampling) of a 64-64
+//               policy for one 128-row tile in one launch, on gemm_fwd's
+//               glds K loop and epilogue helpers: bitwise the three
+//               gemm_fwd calls, without reading h1 / h2 / pdflat back.
 //   dgrad modes (activation 3/4): C = act'(aux) * (X @ Wt) — the
 //               backward chain reuses torch weight layouts directly.
 //   dw_mfma:    dW[out,in] += delta^T @ acts, split-K over row blocks
@@ -505,31 +509,31 @@ __global__ void gemm_fwd_pipe_kernel(FwdArgs a) {
 // address (guide rule 21) — same 64 B cacheline, zero coalescing cost.
 // ---------------------------------------------------------------------------
 
-template <int RING,   // ring depth: 2 (24 KB, 6 blocks/CU — overlap via
-                      // MORE co-resident blocks), 3 (36 KB, 4 blocks/CU,
-                      // default), 4 (48 KB, 3 blocks/CU — deeper
-                      // in-flight staging; measured slower)
-          bool ENV = false>  // fused env-step epilogue (activation 5) — its
-                             // own instantiation, so the layer GEMMs'
-                             // registers and occupancy do not see it
-__launch_bounds__(FWD_WAVES * 64, RING == 2 ? 6 : RING == 3 ? 4 : 3)
-__global__ void gemm_fwd_glds_kernel(FwdArgs a) {
-  constexpr int NT = 2;
-  constexpr int PBK = 16;
-  constexpr int NW = NT * M_WAVE;          // 64
-  constexpr int XB = FWD_M * PBK * 4;      // 8192 B
-  constexpr int WB = PBK * NW * 4;         // 4096 B
-  constexpr int SLOT = XB + WB;
-  __shared__ __attribute__((aligned(16))) char smem[RING * SLOT];
+constexpr int GLDS_NT = 2;
+constexpr int GLDS_BK = 16;
+constexpr int GLDS_NW = GLDS_NT * M_WAVE;        // 64
+constexpr int GLDS_XB = FWD_M * GLDS_BK * 4;     // 8192 B
+constexpr int GLDS_WB = GLDS_BK * GLDS_NW * 4;   // 4096 B
+constexpr int GLDS_SLOT = GLDS_XB + GLDS_WB;
+
+// The streaming K loop of one [128 rows][64 cols] tile: stage ring, K tail
+// and per-block K-phase rotation.  Shared by gemm_fwd_glds_kernel and the
+// fused policy forward, so both run the same MFMA chain.  Returns with
+// every glds landed and the block past a barrier: acc is live and the ring
+// (smem, RING * GLDS_SLOT bytes) is dead.
+template <int RING>
+DEV_INLINE void glds_fwd_mainloop(const FwdArgs& a, char* smem, int64_t b0,
+                                  int n0, f32x16 (&acc)[GLDS_NT]) {
+  constexpr int NT = GLDS_NT;
+  constexpr int PBK = GLDS_BK;
+  constexpr int NW = GLDS_NW;
+  constexpr int XB = GLDS_XB;
+  constexpr int SLOT = GLDS_SLOT;
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wave = tid / WAVE;
   const int i_l = lane & 31;
   const int k_l = lane >> 5;
-  const int n0 = blockIdx.y * NW;
-
-  const int64_t b0 = (int64_t)blockIdx.x * FWD_M;
-  if (b0 >= a.B) return;
 
   // per-thread glds sources (constant; advance by kb each stage)
   // X: two 16-B pieces per thread; dest piece q = tid + p*256 ->
@@ -593,7 +597,6 @@ __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
   for (int p = 0; p < RING - 1; ++p)
     if (p < S) issue(p);
 
-  f32x16 acc[NT];
   #pragma unroll
   for (int t = 0; t < NT; ++t)
     #pragma unroll
@@ -637,6 +640,56 @@ __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
+}
+
+// bias + activation of one accumulator element (layer modes 0 relu,
+// 1 tanh, 2 none)
+DEV_INLINE float fwd_bias_act(float acc, float bv, int activation) {
+  float x = acc + bv;
+  if (activation == 0) x = fmaxf(x, 0.f);
+  else if (activation == 1) x = fast_tanhf(x);
+  return x;
+}
+
+// one output element by heads mode: 2 = padded heads (v at column N-2,
+// columns >= N-1 are the zero-weight pad, discarded), 1 = v at N-1
+DEV_INLINE void fwd_store(float* C, float* v, int heads, int N, int ldc,
+                          int64_t row, int col, float x) {
+  if (heads == 2) {
+    if (col == N - 2) v[row] = x;
+    else if (col < N - 2) C[row * ldc + col] = x;
+  } else if (heads) {
+    if (col == N - 1) v[row] = x;
+    else C[row * ldc + col] = x;
+  } else {
+    C[row * ldc + col] = x;
+  }
+}
+
+template <int RING,   // ring depth: 2 (24 KB, 6 blocks/CU — overlap via
+                      // MORE co-resident blocks), 3 (36 KB, 4 blocks/CU,
+                      // default), 4 (48 KB, 3 blocks/CU — deeper
+                      // in-flight staging; measured slower)
+          bool ENV = false>  // fused env-step epilogue (activation 5) — its
+                             // own instantiation, so the layer GEMMs'
+                             // registers and occupancy do not see it
+__launch_bounds__(FWD_WAVES * 64, RING == 2 ? 6 : RING == 3 ? 4 : 3)
+__global__ void gemm_fwd_glds_kernel(FwdArgs a) {
+  constexpr int NT = GLDS_NT;
+  constexpr int NW = GLDS_NW;
+  constexpr int SLOT = GLDS_SLOT;
+  __shared__ __attribute__((aligned(16))) char smem[RING * SLOT];
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wave = tid / WAVE;
+  const int i_l = lane & 31;
+  const int n0 = blockIdx.y * NW;
+
+  const int64_t b0 = (int64_t)blockIdx.x * FWD_M;
+  if (b0 >= a.B) return;
+
+  f32x16 acc[NT];
+  glds_fwd_mainloop<RING>(a, smem, b0, n0, acc);
 
   if constexpr (ENV) {
     // Fused env step.  The accumulator layout (lane = column) would make
@@ -808,20 +861,196 @@ __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
             x = acc[t][r] * ((a.activation == 3) ? (1.f - h * h)
                                                  : (h > 0.f ? 1.f : 0.f));
           } else {
-            x = acc[t][r] + bv;
-            if (a.activation == 0) x = fmaxf(x, 0.f);
-            else if (a.activation == 1) x = fast_tanhf(x);
+            x = fwd_bias_act(acc[t][r], bv, a.activation);
           }
-          if (a.heads == 2) {
-            if (col == a.N - 2) a.v[row] = x;
-            else if (col < a.N - 2) a.C[row * a.ldc + col] = x;
-          } else if (a.heads) {
-            if (col == a.N - 1) a.v[row] = x;
-            else a.C[row * a.ldc + col] = x;
-          } else {
-            a.C[row * a.ldc + col] = x;
-          }
+          fwd_store(a.C, a.v, a.heads, a.N, a.ldc, row, col, x);
         }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Fused policy forward: L1 -> L2 -> heads (-> action sampling) for one
+// 128-row tile, one launch.  L1 is gemm_fwd_glds_kernel<3>'s K loop
+// (glds_fwd_mainloop); it ends with two accumulator tiles live and the
+// 36 KB ring dead.  Each wave then keeps its own 32 rows in a private LDS
+// image inside the ring and runs the two 64-deep products on it with the
+// same MFMA and the same stage order as the split calls, so h1, h2, pdflat
+// and v are bitwise what three gemm_fwd calls give — but the forward never
+// reads h1 / h2 / pdflat back from HBM, and with SAMPLE the rollout's
+// sample_kernel launch goes too.
+//
+// Image: [32 rows][IMG_LD = 65] floats per wave (4 x 8320 B = 33280 B).
+// ds_write_b32 of an accumulator register: a 32-lane half writes 32
+// consecutive columns of one row — 32 banks.  The A-fragment ds_read_b32:
+// a half reads one column of 32 rows, stride 65 = 1 (mod 32) — 32 banks
+// (an unpadded stride of 64 would put them all on one).  The two halves
+// of either instruction never conflict.  A wave touches only its own
+// image and its LDS operations complete in order, so nothing after the
+// K loop needs a block barrier.
+//
+// B fragments of the two small products come straight from global: W2t
+// and WhT are 16 KB each and L2-resident, 128 B per half-wave per load,
+// and the four waves per SIMD cover the latency.
+// ---------------------------------------------------------------------------
+
+constexpr int IMG_LD = 65;
+
+struct MlpFwdArgs {
+  FwdArgs l1;          // X, Wt = W1t [D][64], bias = b1, C = h1, B, K = D
+  const float* W2t;    // [64][64]
+  const float* b2;     // [64]
+  float* h2;           // [B][64]
+  const float* WhT;    // [64][NH] padded transposed heads, NH = 2A + 2
+  const float* bh;     // [NH]
+  float* pdflat;       // [B][NH - 2]
+  float* v;            // [B]
+  int NH;
+  // SAMPLE only (sample_kernel's arguments)
+  float* actions;      // [B][A]
+  float* xva;          // [B][xva_w]
+  const long long* seed_dev;
+  const float* eps_dev;
+  int step, xva_w, va_off;
+  float act_low, act_high;
+};
+
+// counter-based uniform in (0, 1] — rollout.hip's rng_uniform
+DEV_INLINE float g_rng_uniform(unsigned seed, int env, int step, int slot) {
+  const unsigned h = g_lowbias32(seed ^ (unsigned)env * 0x9E3779B9U ^
+                                 (unsigned)step * 0x85EBCA6BU ^
+                                 (unsigned)slot * 0xC2B2AE35U);
+  return ((h >> 8) + 1) * (1.0f / 16777217.0f);
+}
+
+// acc = image[32][64] @ W[64][N] in the split call's order: four 16-wide
+// k-stages starting at stage `phase`, k ascending inside a stage.  Columns
+// >= N read a clamped (valid) column and are discarded by the caller;
+// tile 1 is skipped when N <= 32 (wave-uniform).
+DEV_INLINE void img_gemm64(const float* img, const float* __restrict__ W,
+                           int N, int phase, int lane,
+                           f32x16 (&acc)[GLDS_NT]) {
+  const int i_l = lane & 31;
+  const int k_l = lane >> 5;
+  #pragma unroll
+  for (int t = 0; t < GLDS_NT; ++t)
+    #pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  const int c0 = i_l < N ? i_l : N - 1;
+  const int c1 = M_WAVE + i_l < N ? M_WAVE + i_l : N - 1;
+  const bool two = N > M_WAVE;
+  #pragma unroll 1
+  for (int s = 0; s < 4; ++s) {
+    const int kb = ((s + phase) & 3) * GLDS_BK;
+    #pragma unroll
+    for (int k2 = 0; k2 < GLDS_BK; k2 += 2) {
+      const int k = kb + k2 + k_l;
+      const float av = img[i_l * IMG_LD + k];
+      const float b0v = W[k * N + c0];
+      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0v, acc[0], 0, 0, 0);
+      if (two) {
+        const float b1v = W[k * N + c1];
+        acc[1] =
+            __builtin_amdgcn_mfma_f32_32x32x2f32(av, b1v, acc[1], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// hidden-layer epilogue (N = 64): act(acc + b) to global rows < B and to
+// the wave's image
+DEV_INLINE void hidden_epilogue(const f32x16 (&acc)[GLDS_NT],
+                                const float* __restrict__ bias,
+                                int activation, float* C, float* img,
+                                int64_t row0, int64_t B, int lane) {
+  #pragma unroll
+  for (int t = 0; t < GLDS_NT; ++t) {
+    const int col = t * M_WAVE + (lane & 31);
+    const float bv = bias[col];
+    #pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int lr = cd_row(r, lane);
+      const float x = fwd_bias_act(acc[t][r], bv, activation);
+      if (row0 + lr < B) C[(row0 + lr) * GLDS_NW + col] = x;
+      img[lr * IMG_LD + col] = x;
+    }
+  }
+}
+
+template <bool SAMPLE>
+__launch_bounds__(FWD_WAVES * 64, 4)
+__global__ void mlp_fwd_fused_kernel(MlpFwdArgs m) {
+  constexpr int RING = 3;
+  static_assert(RING * GLDS_SLOT >= FWD_WAVES * M_WAVE * IMG_LD * 4,
+                "per-wave images must fit the dead stage ring");
+  __shared__ __attribute__((aligned(16))) char smem[RING * GLDS_SLOT];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int64_t b0 = (int64_t)blockIdx.x * FWD_M;
+  const int64_t B = m.l1.B;
+  if (b0 >= B) return;
+
+  f32x16 acc[GLDS_NT];
+  glds_fwd_mainloop<RING>(m.l1, smem, b0, 0, acc);
+
+  float* img = reinterpret_cast<float*>(smem) + wave * (M_WAVE * IMG_LD);
+  const int64_t row0 = b0 + wave * M_WAVE;
+  const int act = m.l1.activation;
+  // the split L2 / heads calls rotate their four stages by the row block
+  // (glds kernel); heads of N <= 32 take the unrotated pipe kernel there
+  const int phase = (int)(blockIdx.x & 3u);
+  const int hphase = m.NH > M_WAVE ? phase : 0;
+
+  hidden_epilogue(acc, m.l1.bias, act, m.l1.C, img, row0, B, lane);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  img_gemm64(img, m.W2t, GLDS_NW, phase, lane, acc);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  hidden_epilogue(acc, m.b2, act, m.h2, img, row0, B, lane);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  img_gemm64(img, m.WhT, m.NH, hphase, lane, acc);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+  // heads epilogue (heads mode 2, no activation)
+  const int NH = m.NH;
+  #pragma unroll
+  for (int t = 0; t < GLDS_NT; ++t) {
+    const int col = t * M_WAVE + (lane & 31);
+    if (col < NH) {
+      const float bv = m.bh[col];
+      #pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int lr = cd_row(r, lane);
+        const float x = fwd_bias_act(acc[t][r], bv, 2);
+        if (row0 + lr < B)
+          fwd_store(m.pdflat, m.v, 2, NH, NH - 2, row0 + lr, col, x);
+        if constexpr (SAMPLE) img[lr * IMG_LD + col] = x;
+      }
+    }
+  }
+
+  if constexpr (SAMPLE) {
+    // sample_kernel's per-(env, j) work on the pd tile in the image
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const unsigned seed = (unsigned)*m.seed_dev;
+    const float eps = *m.eps_dev;
+    const int A = (NH - 2) >> 1;
+    const int step = m.step;
+    for (int idx = lane; idx < M_WAVE * A; idx += WAVE) {
+      const int lr = idx / A;
+      const int j = idx - lr * A;
+      const int64_t e = row0 + lr;
+      if (e < B) {
+        const float mean = img[lr * IMG_LD + j];
+        const float logstd = img[lr * IMG_LD + A + j];
+        float a_ = mean + __expf(logstd) * g_rng_normal(seed, (int)e, step, j);
+        const float u_dec = g_rng_uniform(seed, (int)e, step, 90001);
+        if (u_dec < eps) {
+          const float u = g_rng_uniform(seed, (int)e, step, 90010 + j);
+          a_ = m.act_low + (m.act_high - m.act_low) * u;
+        }
+        m.actions[e * A + j] = a_;
+        m.xva[e * m.xva_w + m.va_off + j] = a_;
       }
     }
   }
@@ -1388,6 +1617,92 @@ void gemm_fwd(torch::Tensor X, torch::Tensor Wt, torch::Tensor bias,
     }
   }
   #undef DISPATCH_FWD
+}
+
+bool mlp_fwd_fused_supported(int64_t D, int64_t H1, int64_t H2, int64_t A) {
+  const int64_t NH = 2 * A + 2;
+  return D >= 4 && D % 4 == 0 && H1 == GLDS_NW && H2 == GLDS_NW && A >= 1 &&
+         NH % 4 == 0 && NH <= GLDS_NW;
+}
+
+void mlp_fwd_fused(torch::Tensor X, torch::Tensor W1t, torch::Tensor b1,
+                   torch::Tensor W2t, torch::Tensor b2, torch::Tensor WhT_pad,
+                   torch::Tensor bh_pad, int64_t act_code, torch::Tensor h1,
+                   torch::Tensor h2, torch::Tensor pdflat, torch::Tensor v,
+                   torch::Tensor actions, torch::Tensor xva,
+                   torch::Tensor seed_dev, torch::Tensor eps_dev, int64_t step,
+                   int64_t va_off, double act_low, double act_high) {
+  // actions non-empty: also sample (rollout); empty: forward only
+  TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.scalar_type() == torch::kFloat);
+  const int64_t B = X.size(0);
+  const int64_t D = X.size(1);
+  TORCH_CHECK(B >= 1 && WhT_pad.dim() == 2);
+  const int64_t NH = WhT_pad.size(1);
+  const int64_t A = (NH - 2) / 2;
+  TORCH_CHECK(NH == 2 * A + 2 && mlp_fwd_fused_supported(D, W1t.size(1),
+                                                          W2t.size(1), A),
+              "mlp_fwd_fused: shape not eligible");
+  TORCH_CHECK(act_code == 0 || act_code == 1, "mlp_fwd_fused: tanh or relu");
+  for (const auto& t : {X, W1t, b1, W2t, b2, WhT_pad, bh_pad, h1, h2, pdflat, v})
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                t.scalar_type() == torch::kFloat);
+  TORCH_CHECK(W1t.dim() == 2 && W1t.size(0) == D && W2t.dim() == 2 &&
+              W2t.size(0) == GLDS_NW && WhT_pad.size(0) == GLDS_NW);
+  TORCH_CHECK(b1.numel() == GLDS_NW && b2.numel() == GLDS_NW &&
+              bh_pad.numel() == NH);
+  TORCH_CHECK(h1.numel() == B * GLDS_NW && h2.numel() == B * GLDS_NW &&
+              pdflat.numel() == B * (NH - 2) && v.numel() == B);
+
+  MlpFwdArgs m{};
+  m.l1.X = X.data_ptr<float>();
+  m.l1.Wt = W1t.data_ptr<float>();
+  m.l1.bias = b1.data_ptr<float>();
+  m.l1.C = h1.data_ptr<float>();
+  m.l1.B = B;
+  m.l1.K = static_cast<int>(D);
+  m.l1.N = GLDS_NW;
+  m.l1.activation = static_cast<int>(act_code);
+  m.l1.ldc = GLDS_NW;
+  m.W2t = W2t.data_ptr<float>();
+  m.b2 = b2.data_ptr<float>();
+  m.h2 = h2.data_ptr<float>();
+  m.WhT = WhT_pad.data_ptr<float>();
+  m.bh = bh_pad.data_ptr<float>();
+  m.pdflat = pdflat.data_ptr<float>();
+  m.v = v.data_ptr<float>();
+  m.NH = static_cast<int>(NH);
+  const bool sample = actions.numel() > 0;
+  if (sample) {
+    TORCH_CHECK(actions.is_cuda() && actions.is_contiguous() &&
+                actions.scalar_type() == torch::kFloat &&
+                actions.numel() == B * A);
+    TORCH_CHECK(xva.is_cuda() && xva.is_contiguous() && xva.dim() == 2 &&
+                xva.scalar_type() == torch::kFloat && xva.size(0) == B &&
+                va_off >= 0 && va_off + A <= xva.size(1));
+    TORCH_CHECK(seed_dev.is_cuda() && seed_dev.scalar_type() == torch::kLong &&
+                seed_dev.numel() == 1 && eps_dev.is_cuda() &&
+                eps_dev.scalar_type() == torch::kFloat &&
+                eps_dev.numel() == 1);
+    m.actions = actions.data_ptr<float>();
+    m.xva = xva.data_ptr<float>();
+    m.seed_dev =
+        reinterpret_cast<const long long*>(seed_dev.data_ptr<int64_t>());
+    m.eps_dev = eps_dev.data_ptr<float>();
+    m.step = static_cast<int>(step);
+    m.xva_w = static_cast<int>(xva.size(1));
+    m.va_off = static_cast<int>(va_off);
+    m.act_low = static_cast<float>(act_low);
+    m.act_high = static_cast<float>(act_high);
+  }
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  const int64_t tiles = (B + FWD_M - 1) / FWD_M;
+  TORCH_CHECK(tiles <= (1 << 22));
+  if (sample)
+    hipLaunchKernelGGL(mlp_fwd_fused_kernel<true>, dim3((unsigned)tiles),
+                       dim3(FWD_WAVES * 64), 0, stream, m);
+  else
+    hipLaunchKernelGGL(mlp_fwd_fused_kernel<false>, dim3((unsigned)tiles),
+                       dim3(FWD_WAVES * 64), 0, stream, m);
 }
 
 void gemm_env_step(torch::Tensor xva, torch::Tensor M, torch::Tensor xin,

@@ -617,6 +617,56 @@ class DPPOEngine:
         opt-in."""
         return os.environ.get("DPPO_XV_FOLD", "0") == "1"
 
+    # the DPPO_FWD_FUSED default: what profiles/r06_fwd_fused.txt measured
+    FWD_FUSED_DEFAULT = "1"
+
+    def _fwd_fused(self) -> bool:
+        """DPPO_FWD_FUSED=0|1: '1' runs the policy forward (L1, L2, heads
+        and, in the rollout, action sampling) as one mlp_fwd_fused launch
+        where the shape is eligible; '0' keeps one gemm_fwd per layer plus
+        rollout_sample.  Both give bitwise-equal results.  Anything else is
+        an error, not a fall-back.  Resolved once per engine and value of
+        the variables it depends on."""
+        key = tuple(os.environ.get(k) for k in (
+            "DPPO_FWD_FUSED", "DPPO_HEADS_PAD", "DPPO_GEMM_GLDS"))
+        cached = getattr(self, "_fwd_fused_cache", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        on = self._resolve_fwd_fused(
+            key[0] if key[0] is not None else self.FWD_FUSED_DEFAULT)
+        self._fwd_fused_cache = (key, on)
+        return on
+
+    def _resolve_fwd_fused(self, mode: str) -> bool:
+        from .ops import hip_ext
+
+        if mode not in ("0", "1"):
+            raise ValueError(f"DPPO_FWD_FUSED={mode!r}: expected '0' or '1'")
+        if mode == "0":
+            return False
+        c = self.cfg
+        if self._act_kind != "box" or c.DTYPE != "float32":
+            return False
+        if c.ACTIVATION not in ("tanh", "relu"):
+            return False
+        # the fused kernel reproduces the order of the default split chain
+        # (padded heads on the glds kernel); with either switched off the
+        # split chain accumulates in another order, so stay on it
+        if (os.environ.get("DPPO_HEADS_PAD") == "0"
+                or os.environ.get("DPPO_GEMM_GLDS", "1") == "0"):
+            return False
+        hs = tuple(c.HIDDEN_SIZES)
+        return len(hs) == 2 and bool(hip_ext().mlp_fwd_fused_supported(
+            self.obs_space.shape[0], hs[0], hs[1], self.act_space.shape[0]))
+
+    def _count_fwd_fused(self, use: str) -> None:
+        """Launch counter per use ('rollout', 'boot', 'update'): lets tests
+        assert which path ran."""
+        cnt = getattr(self, "fwd_fused_launches", None)
+        if cnt is None:
+            cnt = self.fwd_fused_launches = {}
+        cnt[use] = cnt.get(use, 0) + 1
+
     def _v3_body(self, states, pdflats, actions, values, rewards, dones,
                  boot_v):
         """Capture-safe per-step rollout pipeline.  RNG slots match the
@@ -659,29 +709,42 @@ class DPPOEngine:
         fused = self._env_fused()
         fold = fused and self._xv_fold() and v3["xvp"] is not None
         no_fold = (v3["empty"], v3["empty"])
+        # one launch for L1 + L2 + heads + sampling (bitwise equal to the
+        # per-layer chain + rollout_sample; see mlp_fwd_fused_kernel)
+        fwd_fused = whT_pad is not None and self._fwd_fused()
+        hb = [lay.bias.detach() for lay in self.pi.hidden]
         for st in range(T):
             xin = states[st]
             h = xin
-            for l in range(n_h):
-                hl = acts_views[l].narrow(0, st * E, E)
-                ext.gemm_fwd(h, wts[l],
-                             self.pi.hidden[l].bias.detach(), act_code, 0,
-                             hl, hl, hl, 0, 0, 0)
-                h = hl
-            if whT_pad is not None:
-                ext.gemm_fwd(h, whT_pad, v3["bh_pad"], 2, 2, pdflats[st],
-                             values[st], pdflats[st], 0, 0, 0)
+            if fwd_fused:
+                ext.mlp_fwd_fused(
+                    xin, wts[0], hb[0], wts[1], hb[1], whT_pad, v3["bh_pad"],
+                    act_code, acts_views[0].narrow(0, st * E, E),
+                    acts_views[1].narrow(0, st * E, E), pdflats[st],
+                    values[st], actions[st], v3["xva"], v3["seed_dev"],
+                    v3["eps_dev"], st, v3["va_off"], low, high)
+                self._count_fwd_fused("rollout")
             else:
-                ext.gemm_fwd(h, wh, bh, 2, 1, pdflats[st], values[st],
-                             pdflats[st], 1, 0, 0)
+                for l in range(n_h):
+                    hl = acts_views[l].narrow(0, st * E, E)
+                    ext.gemm_fwd(h, wts[l], hb[l], act_code, 0,
+                                 hl, hl, hl, 0, 0, 0)
+                    h = hl
+                if whT_pad is not None:
+                    ext.gemm_fwd(h, whT_pad, v3["bh_pad"], 2, 2, pdflats[st],
+                                 values[st], pdflats[st], 0, 0, 0)
+                else:
+                    ext.gemm_fwd(h, wh, bh, 2, 1, pdflats[st], values[st],
+                                 pdflats[st], 1, 0, 0)
             # XV = x @ V into the concat buffer's first rank columns; with
             # the fold, step st-1's env epilogue already left it there
             if not fold or st == 0:
                 ext.gemm_fwd(xin, v3["V"], v3["bz_r"], 2, 0, v3["xva"],
                              v3["xva"], v3["xva"], 0, 0, v3["kw"])
-            ext.rollout_sample(pdflats[st], actions[st], v3["xva"],
-                               v3["seed_dev"], v3["eps_dev"], st,
-                               v3["va_off"], low, high)
+            if not fwd_fused:
+                ext.rollout_sample(pdflats[st], actions[st], v3["xva"],
+                                   v3["seed_dev"], v3["eps_dev"], st,
+                                   v3["va_off"], low, high)
             # the env transition reads states[st] and writes states[st+1]
             # directly (policy input already comes from the blob) — env.x
             # only receives the FINAL state, for the bootstrap forward and
@@ -711,10 +774,17 @@ class DPPOEngine:
                                      float(env.NOISE), st)
         # bootstrap value V(x_T)
         h = env.x
+        if fwd_fused:
+            ext.mlp_fwd_fused(
+                h, wts[0], hb[0], wts[1], hb[1], whT_pad, v3["bh_pad"],
+                act_code, v3["h"][0], v3["h"][1], v3["pd_scratch"], boot_v,
+                v3["empty"], v3["empty"], v3["seed_dev"], v3["eps_dev"], 0,
+                0, 0.0, 0.0)
+            self._count_fwd_fused("boot")
+            return ext.rollout_moments(rewards, dones, v3["epr_before"], T, E)
         for l in range(n_h):
             hl = v3["h"][l]
-            ext.gemm_fwd(h, wts[l],
-                         self.pi.hidden[l].bias.detach(), act_code, 0,
+            ext.gemm_fwd(h, wts[l], hb[l], act_code, 0,
                          hl, hl, hl, 0, 0, 0)
             h = hl
         if whT_pad is not None:
@@ -1602,18 +1672,35 @@ class DPPOEngine:
         total = sum(B * dims[l + 1] for l in range(n_hidden))
         acts = torch.empty(total, device=states.device, dtype=states.dtype)
         a_views, o = [], 0
-        x = states
         for l in range(n_hidden):
             n = B * dims[l + 1]
-            cview = acts.narrow(0, o, n).view(B, dims[l + 1])
-            ext.gemm_fwd(x, wts[l], bs[l],
-                         act_code, 0, cview, cview, cview, 0, 0, 0)
-            x = cview
-            a_views.append(cview)
+            a_views.append(acts.narrow(0, o, n).view(B, dims[l + 1]))
             o += n
         P = 2 * self.act_space.shape[0]
         pdflat = torch.empty(B, P, device=states.device, dtype=states.dtype)
         v = torch.empty(B, device=states.device, dtype=states.dtype)
+        if self._fwd_fused():
+            # one launch: h1 / h2 are written once for the backward and
+            # never read back by the forward
+            with torch.no_grad():
+                WhT_pad = torch.zeros(Wh_cat.shape[1], P + 2,
+                                      device=states.device)
+                WhT_pad[:, :P + 1] = Wh_cat.t()
+                bh2 = torch.zeros(P + 2, device=states.device)
+                bh2[:P + 1] = bh
+            empty = states.new_empty(0)
+            ext.mlp_fwd_fused(states, wts[0], bs[0], wts[1], bs[1], WhT_pad,
+                              bh2, act_code, a_views[0], a_views[1], pdflat,
+                              v, empty, empty, empty, empty, 0, 0, 0.0, 0.0)
+            self._count_fwd_fused("update")
+            self._Wh_pad = Wh_pad
+            return acts, a_views, v, pdflat
+        x = states
+        for l in range(n_hidden):
+            ext.gemm_fwd(x, wts[l], bs[l],
+                         act_code, 0, a_views[l], a_views[l], a_views[l],
+                         0, 0, 0)
+            x = a_views[l]
         if (P + 2) % 4 == 0 and os.environ.get("DPPO_HEADS_PAD") != "0":
             # padded transposed heads (N=P+2, %4==0): glds kernel with
             # heads mode 2 instead of the layout-1 pipe kernel
