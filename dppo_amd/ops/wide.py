@@ -23,6 +23,8 @@ from typing import List
 
 import torch
 
+from ..utils.graphs import warm_and_capture
+
 
 def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
@@ -60,6 +62,13 @@ class WideBF16Path:
         self.bhcat = torch.empty(self.P + 1, device=self.dev)
         self._fwd_bufs = {}
         self._upd = None
+        # captured update: the graph, whether its capture failed, and
+        # whether it was captured with step 1 skipping its forward
+        self._graph = None
+        self._graph_failed = False
+        self._graph_skip_first = None
+        # the rollout's recording pass dual-wrote the transposed h
+        self._hT_from_rollout = False
 
     # -- weights -------------------------------------------------------
     def mark_dirty(self) -> None:
@@ -191,14 +200,6 @@ class WideBF16Path:
         B = batch.states.shape[0]
         u = self._upd_bufs(B)
         clip = cfg.CLIP_PARAM * l_mul
-        nH = len(self.H)
-        flat = eng.flat_pi
-        offsets = [sl.start for sl in flat.slices]
-        w_off = [offsets[2 * l] for l in range(nH)]
-        b_off = [offsets[2 * l + 1] for l in range(nH)]
-        off_wv, off_bv = offsets[2 * nH], offsets[2 * nH + 1]
-        off_wp, off_bp = offsets[2 * nH + 2], offsets[2 * nH + 3]
-        grad = flat.flat_grad
 
         # per-round inputs (constant across the UPDATE_STEPS epochs),
         # copied into persistent buffers so the captured graph sees them
@@ -212,20 +213,19 @@ class WideBF16Path:
         u["clip_dev"].fill_(clip)
         eng.optimizer.lr_dev.fill_(float(eng.optimizer.param_groups[0]["lr"]))
 
-        import os as _os
-        # hipGraph capture of a multi-stream (event-forked) body segfaults
-        # in capture_end on this ROCm build, so the captured variant runs
-        # the SEQUENTIAL body (measured fastest: the side-stream overlap
-        # bought nothing — the 1-block/CU GEMMs leave no residency for
-        # co-scheduled transpose blocks).  DPPO_WIDE_GRAPH=0 opts out.
+        # The body is sequential on one stream: hipGraph capture of a
+        # multi-stream (event-forked) body segfaulted in capture_end, and
+        # overlapping the transposes on a side stream bought nothing (the
+        # 1-block/CU GEMMs leave no residency for co-scheduled transpose
+        # blocks).  DPPO_WIDE_GRAPH=0 opts out of the capture.
         graph_ok = (cfg.USE_GRAPHS
-                    and _os.environ.get("DPPO_WIDE_GRAPH") != "0"
+                    and os.environ.get("DPPO_WIDE_GRAPH") != "0"
                     and (not eng.comm.distributed
-                         or _os.environ.get("DPPO_GRAPH_DIST") == "1")
-                    and not getattr(self, "_graph_failed", False))
-        skip_now = bool(getattr(eng, "_wide_rollout_h_valid", False))
+                         or os.environ.get("DPPO_GRAPH_DIST") == "1")
+                    and not self._graph_failed)
+        skip_now = eng._wide_rollout_h_valid
         if graph_ok:
-            if getattr(self, "_graph_skip_first", None) is not None and \
+            if self._graph_skip_first is not None and \
                     self._graph_skip_first != skip_now:
                 self._graph = None  # recapture with the new structure
             if self._graph is None:
@@ -248,38 +248,15 @@ class WideBF16Path:
         """Capture the UPDATE_STEPS pipeline once (device-state Adam,
         clip from clip_dev; warmup executes real steps so param/optimizer
         state is snapshot/restored around it)."""
-        eng = self.eng
-        opt = eng.optimizer
-        snap = (eng.flat_pi.flat_param.detach().clone(), opt.exp_avg.clone(),
-                opt.exp_avg_sq.clone(), opt.step_dev.clone())
-        try:
-            warm = torch.cuda.Stream()
-            warm.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(warm):
-                self._update_body(u, overlap=False)
-            torch.cuda.current_stream().wait_stream(warm)
-            torch.cuda.synchronize()
-        finally:
-            with torch.no_grad():
-                eng.flat_pi.flat_param.copy_(snap[0])
-                opt.exp_avg.copy_(snap[1])
-                opt.exp_avg_sq.copy_(snap[2])
-                opt.step_dev.copy_(snap[3])
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._update_body(u, overlap=False)
-        self._graph = g
-        self._graph_skip_first = bool(
-            getattr(self.eng, "_wide_rollout_h_valid", False))
+        (self._graph,) = warm_and_capture(
+            self.eng._train_state(), lambda: self._update_body(u),
+            [lambda: self._update_body(u)])
+        self._graph_skip_first = self.eng._wide_rollout_h_valid
 
     @torch.no_grad()
-    def _update_body(self, u, overlap: bool = False) -> None:
-        """UPDATE_STEPS pipeline with the memory-bound transposes and
-        heads-dW overlapped on a side stream: the 256^2 GEMMs run 2
-        waves/SIMD MFMA-bound (6 idle wave slots per SIMD and <1/3 of
-        HBM bandwidth used), so the 4.4 TB/s transpose kernel
-        co-schedules nearly for free.  Cross-stream edges are events
-        (graph capture records them)."""
+    def _update_body(self, u) -> None:
+        """The capture-safe UPDATE_STEPS pipeline, sequential on the
+        current stream."""
         eng, ext, cfg = self.eng, self.ext, self.cfg
         B = u["B"]
         nH = len(self.H)
@@ -290,62 +267,26 @@ class WideBF16Path:
         off_wv, off_bv = offsets[2 * nH], offsets[2 * nH + 1]
         off_wp, off_bp = offsets[2 * nH + 2], offsets[2 * nH + 3]
         grad = flat.flat_grad
-        main = torch.cuda.current_stream()
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream()
-        side = self._side if overlap else main
-        evs = self._evs = []  # keep alive across graph replays
-
-        class _NullCtx:
-            def __enter__(self):
-                return None
-
-            def __exit__(self, *a):
-                return False
-
-        side_ctx = (lambda: torch.cuda.stream(side)) if overlap \
-            else (lambda: _NullCtx())
-
-        def fork():
-            if not overlap:
-                return
-            e = torch.cuda.Event()
-            evs.append(e)
-            e.record(main)
-            side.wait_event(e)
-
-        def join():
-            if not overlap:
-                return None
-            e = torch.cuda.Event()
-            evs.append(e)
-            e.record(side)
-            return e
-
         # When the graphed rollout recorded its activations into u["h"]/
         # u["pd"]/u["v"] (same parameters as step 1 — sync_oldpi then
         # rollout then update, no param change in between), step 1 skips
         # its forward+heads GEMMs entirely.
-        skip_first = bool(getattr(eng, "_wide_rollout_h_valid", False))
+        skip_first = eng._wide_rollout_h_valid
         # transposed-operand dual-writes from the GEMM epilogues (the
         # LDS-repacked stripes store 32 contiguous bytes per column) in
         # place of 8 of the 9 separate transpose passes per step:
         # measured +3.9% same-box (580.5 vs 558.9 K env-steps/s);
         # DPPO_WIDE_DUALW=0 restores the separate transpose passes
-        dualw = os.environ.get("DPPO_WIDE_DUALW", "1") != "0"
+        dualw = self._dualw()
         for step_i in range(cfg.UPDATE_STEPS):
             self.refresh_weights()
             x = u["x"]
-            ev_hT = [None] * nH
             if step_i == 0 and skip_first:
-                if not (dualw and getattr(self, "_hT_from_rollout", False)):
+                if not (dualw and self._hT_from_rollout):
                     for l in range(nH):
-                        fork()
-                        with side_ctx():
-                            ext.bf16_transpose(u["h"][l], u["hT"][l],
-                                               self._f, 0, B, self.H[l],
-                                               self.H[l], B)
-                        ev_hT[l] = join()
+                        ext.bf16_transpose(u["h"][l], u["hT"][l],
+                                           self._f, 0, B, self.H[l],
+                                           self.H[l], B)
             else:
                 for l in range(nH):
                     if dualw:
@@ -358,12 +299,9 @@ class WideBF16Path:
                                        eng.pi.hidden[l].bias.detach(),
                                        self._b, self._f, 0, self._b, 0,
                                        self._f, 0)
-                        fork()
-                        with side_ctx():
-                            ext.bf16_transpose(u["h"][l], u["hT"][l],
-                                               self._f, 0, B, self.H[l],
-                                               self.H[l], B)
-                        ev_hT[l] = join()
+                        ext.bf16_transpose(u["h"][l], u["hT"][l],
+                                           self._f, 0, B, self.H[l],
+                                           self.H[l], B)
                     x = u["h"][l]
                 ext.bf16_mm_small(x, self.whcat, u["pd"], u["v"], self._b,
                                   self._f, 0, 0, 0, 4, B, self.P + 1,
@@ -373,23 +311,17 @@ class WideBF16Path:
                               u["actions"], u["adv"], u["etr"], u["gh"],
                               u["clip_dev"], 0.0, cfg.ENTCOEFF, cfg.VCOEFF)
             flat.zero_grad()
-            # side: ghT (+ head bias colsums) and the whole heads dW —
-            # independent of the main dgrad/dW chain
-            fork()
-            with side_ctx():
-                u["bias_tmp"].zero_()
-                ext.bf16_transpose(u["gh"], u["ghT"], u["bias_tmp"], 0,
-                                   B, self.KP, self.KP, B)
-                grad[off_bp:off_bp + self.P].copy_(u["bias_tmp"][:self.P])
-                grad[off_bv:off_bv + 1].copy_(
-                    u["bias_tmp"][self.P:self.P + 1])
-                if overlap:
-                    side.wait_event(ev_hT[nH - 1])
-                ext.bf16_mm_small(u["ghT"], u["hT"][nH - 1], self._b,
-                                  self._b, self._b, grad, off_wp, off_wv,
-                                  self.P, 5, self.P + 1, self.H[-1], 0,
-                                  self._f)
-            ev_heads = join()
+            # ghT (+ head bias colsums) and the whole heads dW
+            u["bias_tmp"].zero_()
+            ext.bf16_transpose(u["gh"], u["ghT"], u["bias_tmp"], 0,
+                               B, self.KP, self.KP, B)
+            grad[off_bp:off_bp + self.P].copy_(u["bias_tmp"][:self.P])
+            grad[off_bv:off_bv + 1].copy_(
+                u["bias_tmp"][self.P:self.P + 1])
+            ext.bf16_mm_small(u["ghT"], u["hT"][nH - 1], self._b,
+                              self._b, self._b, grad, off_wp, off_wv,
+                              self.P, 5, self.P + 1, self.H[-1], 0,
+                              self._f)
             # heads backward: dz[nH-1] = (gh @ Whcat) * dtanh(h[-1])
             d_cur = u["d0"]
             dT_cur = u["dT0"]
@@ -401,11 +333,8 @@ class WideBF16Path:
                 ext.bf16_mm256(u["gh"], self.whcatT, d_cur, 2, self._f,
                                u["h"][nH - 1], self._f, 0,
                                self._b, 0, self._f, 0)
-                fork()
-                with side_ctx():
-                    ext.bf16_transpose(d_cur, dT_cur, grad, b_off[nH - 1],
-                                       B, self.H[nH - 1], self.H[nH - 1], B)
-                ev_dT = join()
+                ext.bf16_transpose(d_cur, dT_cur, grad, b_off[nH - 1],
+                                   B, self.H[nH - 1], self.H[nH - 1], B)
             # heads gradients are the LAST contiguous flat-grad region
             # (vf.w | vf.b | pi.w | pi.b): all-reduce them as their own
             # bucket as soon as they are complete, overlapping the rest
@@ -414,16 +343,10 @@ class WideBF16Path:
             # tiny flagship grads keep the single fused bucket)
             per_layer_ar = eng.comm.distributed
             if per_layer_ar:
-                if overlap:
-                    main.wait_event(ev_heads)
                 eng.comm.allreduce_mean_(grad[off_wv:])
             # hidden chain (uniform H: buffers are exact-size views)
             for l in range(nH - 1, -1, -1):
                 actT = u["xT"] if l == 0 else u["hT"][l - 1]
-                if overlap:
-                    if l > 0:
-                        main.wait_event(ev_hT[l - 1])
-                    main.wait_event(ev_dT)
                 ext.bf16_mm256(dT_cur, actT, self._b, 3, self._f, self._b,
                                grad, w_off[l], self._b, 0, self._f, 0)
                 if per_layer_ar and l > 0:
@@ -432,8 +355,8 @@ class WideBF16Path:
                     eng.comm.allreduce_mean_(
                         grad[w_off[l]:b_off[l] + self.H[l]])
                 if l > 0:
-                    # dz[l-1] = (dz[l] @ W[l]) * dtanh(h[l-1]); side
-                    # transposes dz[l-1] (+ colsum -> db[l-1])
+                    # dz[l-1] = (dz[l] @ W[l]) * dtanh(h[l-1]), then its
+                    # transpose (+ colsum -> db[l-1])
                     d_nxt = u["d1"] if d_cur is u["d0"] else u["d0"]
                     dT_nxt = u["dT1"] if dT_cur is u["dT0"] else u["dT0"]
                     if dualw:
@@ -444,16 +367,10 @@ class WideBF16Path:
                         ext.bf16_mm256(d_cur, self.Wt_bf[l], d_nxt, 2,
                                        self._f, u["h"][l - 1], self._f, 0,
                                        self._b, 0, self._f, 0)
-                        fork()
-                        with side_ctx():
-                            ext.bf16_transpose(d_nxt, dT_nxt, grad,
-                                               b_off[l - 1], B,
-                                               self.H[l - 1],
-                                               self.H[l - 1], B)
-                        ev_dT = join()
+                        ext.bf16_transpose(d_nxt, dT_nxt, grad,
+                                           b_off[l - 1], B, self.H[l - 1],
+                                           self.H[l - 1], B)
                     d_cur, dT_cur = d_nxt, dT_nxt
-            if overlap and not per_layer_ar:
-                main.wait_event(ev_heads)
             if per_layer_ar:
                 # last bucket: layer 0's W/b (its bias colsum rides dz_0's
                 # transpose which precedes dW_0 in stream order)

@@ -38,6 +38,7 @@ deadlocks.
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import math
 import os
 from dataclasses import dataclass
@@ -50,11 +51,15 @@ from .envs.synthetic import BatchedSyntheticEnv, make_env
 from .models.mlp import PolicyValueMLP  # noqa: F401 (public engine surface)
 from .ops import gae_advantages, ppo_losses, PPOLossCoeffs
 from .parallel.comm import Comm, FlatBuffers
+from .utils.graphs import warm_and_capture
 from .utils.logging import ScalarLogger
 from .utils.timers import PhaseTimers
 from . import spaces
 
 STATS_DIM = 11  # logs[9] + cur_lr + valid
+
+# RolloutBatch's per-sample tensors (leading dim T*E)
+_SAMPLE_FIELDS = ("states", "actions", "adv", "etr", "oldflat", "oldv")
 
 
 @dataclass
@@ -79,6 +84,12 @@ class RolloutBatch:
     ep_max: torch.Tensor
     valid: bool
 
+    def narrow(self, o: int, n: int) -> "RolloutBatch":
+        """Rows [o, o+n) of the per-sample tensors (views); the scalars
+        and episode moments are shared."""
+        return dataclasses.replace(self, **{
+            f: getattr(self, f).narrow(0, o, n) for f in _SAMPLE_FIELDS})
+
 
 class DPPOEngine:
     def __init__(
@@ -96,6 +107,31 @@ class DPPOEngine:
         # DTYPE='bfloat16' switches the update-path GEMM compute to bf16
         # autocast (BASELINE config 5) with fp32 loss math.
         self.dtype = torch.float32
+
+        # Lazily created state, declared here with its "unset" value:
+        self._warned = set()            # _warn_once keys already printed
+        self._wide_path = None          # WideBF16Path (ops/wide.py)
+        self._cat_ctr = 0               # cat_sample RNG counter
+        self._rollout_counter = 0       # rollout seed counter
+        # persistent rollout / GAE outputs (stable addresses for capture)
+        self._rollout_out = self._adv_buf = self._etr_buf = None
+        self._mw = None                 # staged MFMA weight operands
+        self._wh_pad_staged = False     # last staging filled Wh_pad
+        self._v3 = self._v3_key = None  # v3 rollout buffers
+        self._v3_graph = self._v3_moments = None
+        self._v3_graph_failed = False
+        self._v3_acts_valid = False     # v3 rollout recorded activations
+        self._wr = self._wr_key = None  # wide graphed rollout buffers
+        self._wr_graph = None           # False once its capture failed
+        self._wide_rollout_h_valid = False
+        self._fwd_fused_cache = self._mid_mode_cache = None
+        self.fwd_fused_launches = {}    # mlp_fwd_fused launches per use
+        self._clip_dev = None           # device clip for captured updates
+        self._upd_graph = self._upd_graph_skip = None
+        self._graph_failed = False
+        self._mb_graphs = self._mb_key = None
+        self._mb_graph_failed = False
+        self._chunk_slabs = None        # chunk kernel gradient scratch
 
         obs_space, act_space = game_spaces(cfg.GAME)
         self.obs_space, self.act_space = obs_space, act_space
@@ -169,12 +205,9 @@ class DPPOEngine:
     def _warn_once(self, key: str, msg: str) -> None:
         """Rank-0 one-shot warning (graph-capture fallbacks etc. must not
         silently de-optimize production runs — VERDICT r01 weak #5)."""
-        seen = getattr(self, "_warned", None)
-        if seen is None:
-            seen = self._warned = set()
-        if key in seen:
+        if key in self._warned:
             return
-        seen.add(key)
+        self._warned.add(key)
         if self.comm.rank == 0:
             print(f"[dppo_amd] WARNING: {msg}", flush=True)
 
@@ -182,27 +215,37 @@ class DPPOEngine:
     def sync_oldpi(self) -> None:
         """oldpi <- pi, one flat copy (sync_pis, PPO.py:47)."""
         self.flat_old.flat_param.copy_(self.flat_pi.flat_param)
-        if getattr(self, "_wide_path", None) is not None:
+        if self._wide_path is not None:
             # params may have changed since the last rollout (update,
             # drift-guard broadcast, checkpoint restore) — refresh the
             # bf16 weight copies once per round
             self._wide_path.mark_dirty()
+
+    def _hip_path(self, act_kind: str, dtype: str = "float32") -> bool:
+        """HIP kernels in use, this action family, this DTYPE: what the
+        eligibility of every hand-written path opens with."""
+        from .ops import use_hip
+
+        c = self.cfg
+        return (self._act_kind == act_kind and c.DTYPE == dtype
+                and use_hip(self.device, c.USE_HIP_KERNELS))
+
+    @property
+    def _act_code(self) -> int:
+        """Activation code of the HIP kernels: 1 tanh, 0 relu."""
+        return 1 if self.cfg.ACTIVATION == "tanh" else 0
 
     # -- wide bf16 path (BASELINE #5) ----------------------------------
     def _can_wide_bf16(self) -> bool:
         """Eligibility for the hand-written bf16 MFMA path (ops/wide.py +
         ops/hip/bf16_gemm.hip): wide tanh MLP, Box policy, bf16 compute,
         dims in 256-multiples (the 256^2-tile GEMM's shape contract)."""
-        from .ops import use_hip
-
         c = self.cfg
         if os.environ.get("DPPO_WIDE") == "0":  # A/B: autocast/rocBLAS path
             return False
-        if self._act_kind != "box" or c.DTYPE != "bfloat16":
-            return False
         if c.ACTIVATION != "tanh" or c.MINIBATCH_SIZE != 0:
             return False
-        if not use_hip(self.device, c.USE_HIP_KERNELS):
+        if not self._hip_path("box", "bfloat16"):
             return False
         H = c.HIDDEN_SIZES
         if self.obs_space.shape[0] % 256 or any(h % 256 for h in H):
@@ -212,7 +255,7 @@ class DPPOEngine:
         return True
 
     def _wide(self):
-        if getattr(self, "_wide_path", None) is None:
+        if self._wide_path is None:
             from .ops.wide import WideBF16Path
 
             self._wide_path = WideBF16Path(self)
@@ -294,7 +337,7 @@ class DPPOEngine:
             # RNG, one launch, no torch RNG round trips
             from .ops import hip_ext
 
-            self._cat_ctr = getattr(self, "_cat_ctr", 0) + 1
+            self._cat_ctr += 1
             seed = (self.cfg.SEED * 1_000_003
                     + self.comm.rank * 7_919) & 0x7FFFFFFF
             a = hip_ext().cat_sample(pdflat, seed, self._cat_ctr)
@@ -313,12 +356,8 @@ class DPPOEngine:
     def _can_fuse_rollout(self) -> bool:
         """Eligibility for the fused HIP rollout kernel (rollout.hip):
         Box/DiagGaussian policy, dims within kernel limits, fp32, GPU."""
-        from .ops import use_hip
-
         c = self.cfg
-        if self._act_kind != "box" or c.DTYPE != "float32":
-            return False
-        if not use_hip(self.device, c.USE_HIP_KERNELS):
+        if not self._hip_path("box"):
             return False
         if not (1 <= len(c.HIDDEN_SIZES) <= 3):
             return False
@@ -344,12 +383,8 @@ class DPPOEngine:
         dims within kernel limits, fp32, GPU.  Separate from
         _can_fuse_rollout(), which also gates the Box-only v3 rollout and
         graphed update."""
-        from .ops import use_hip
-
         c = self.cfg
-        if self._act_kind != "discrete" or c.DTYPE != "float32":
-            return False
-        if not use_hip(self.device, c.USE_HIP_KERNELS):
+        if not self._hip_path("discrete"):
             return False
         if not (1 <= len(c.HIDDEN_SIZES) <= 3):
             return False
@@ -423,45 +458,7 @@ class DPPOEngine:
         """One rollout iteration in a single fused kernel launch
         (ops/hip/rollout.hip): MLP forward + sampling + epsilon-greedy +
         env dynamics + episode bookkeeping for all T steps."""
-        from .ops import hip_ext
-
-        ext = hip_ext()
-        c, E = self.cfg, self.cfg.NUM_ENVS
-        T = c.MAX_EPOCH_STEPS
-        eps = self.exploration_rate()
-        env = self.env
-        self._rollout_counter = getattr(self, "_rollout_counter", 0) + 1
-        seed = (
-            c.SEED * 1_000_003
-            + self.comm.rank * 7_919
-            + self._rollout_counter * 104_729
-        ) & 0x7FFFFFFFFFFFFFFF
-        low = float(self.act_space.low.flat[0])
-        high = float(self.act_space.high.flat[0])
-        blob, offsets, dims = self._rollout_weight_blob()
-        # persistent output buffers: stable addresses let the update phase
-        # be hipGraph-captured once and replayed every round
-        A = self.act_space.shape[0]
-        D = self.obs_space.shape[0]
-        n_out = T * E * (D + 3 * A + 3) + E + 5
-        if getattr(self, "_rollout_out", None) is None or \
-                self._rollout_out.numel() != n_out:
-            self._rollout_out = torch.empty(n_out, device=self.device)
-            self._adv_buf = torch.empty(T * E, device=self.device)
-            self._etr_buf = torch.empty(T * E, device=self.device)
-        self._v3_acts_valid = False  # fused kernel does not record acts
-        (states, pdflats, actions, values, rewards, dones, boot_v,
-         moments) = ext.rollout_run(
-            blob, offsets, dims,
-            1 if c.ACTIVATION == "tanh" else 0,
-            env.blob, env.rank_eff, env.horizons_i32,
-            float(env.NOISE), low, high, float(eps),
-            env.x, env.t, self.epr, T, A, seed, self._rollout_out, 0,
-        )
-        self.obs = env.x  # updated in place by the kernel
-        return self._finish_hip_rollout(
-            states, pdflats, actions, values, rewards, dones, boot_v,
-            moments, eps)
+        return self._rollout_once_fused(cat=False)
 
     @torch.no_grad()
     def _rollout_once_hip_cat(self) -> Tuple[RolloutBatch, Dict[str, float]]:
@@ -469,6 +466,36 @@ class DPPOEngine:
         Categorical instantiation of rollout.hip): MLP forward + Gumbel-max
         sampling + epsilon-greedy + env dynamics + episode bookkeeping for
         all T steps; int64 action indices come straight from the kernel."""
+        return self._rollout_once_fused(cat=True)
+
+    def _next_rollout_seed(self) -> int:
+        """Seed of the next HIP rollout: SEED, rank and a per-engine
+        rollout counter, which this bumps."""
+        self._rollout_counter += 1
+        return (
+            self.cfg.SEED * 1_000_003
+            + self.comm.rank * 7_919
+            + self._rollout_counter * 104_729
+        ) & 0x7FFFFFFFFFFFFFFF
+
+    def _rollout_outputs(self, n_out: int) -> torch.Tensor:
+        """Persistent rollout output blob of n_out floats (and the GAE
+        outputs next to it): stable addresses let the update phase be
+        hipGraph-captured once and replayed every round."""
+        if self._rollout_out is None or self._rollout_out.numel() != n_out:
+            B = self.cfg.MAX_EPOCH_STEPS * self.cfg.NUM_ENVS
+            self._rollout_out = torch.empty(n_out, device=self.device)
+            self._adv_buf = torch.empty(B, device=self.device)
+            self._etr_buf = torch.empty(B, device=self.device)
+        return self._rollout_out
+
+    def _act_bounds(self) -> Tuple[float, float]:
+        return (float(self.act_space.low.flat[0]),
+                float(self.act_space.high.flat[0]))
+
+    def _rollout_once_fused(self, cat: bool):
+        """The single-launch rollout of either policy family: Categorical
+        (`cat`) or DiagGaussian, which also takes the action bounds."""
         from .ops import hip_ext
 
         ext = hip_ext()
@@ -476,31 +503,27 @@ class DPPOEngine:
         T = c.MAX_EPOCH_STEPS
         eps = self.exploration_rate()
         env = self.env
-        self._rollout_counter = getattr(self, "_rollout_counter", 0) + 1
-        seed = (
-            c.SEED * 1_000_003
-            + self.comm.rank * 7_919
-            + self._rollout_counter * 104_729
-        ) & 0x7FFFFFFFFFFFFFFF
+        seed = self._next_rollout_seed()
         blob, offsets, dims = self._rollout_weight_blob()
-        K = self.act_space.n
         D = self.obs_space.shape[0]
-        # actions(int64) | states | logits | values | rewards | dones |
-        # boot | moments, in floats
-        n_out = T * E * (2 + D + K + 3) + E + 5
-        if getattr(self, "_rollout_out", None) is None or \
-                self._rollout_out.numel() != n_out:
-            self._rollout_out = torch.empty(n_out, device=self.device)
-            self._adv_buf = torch.empty(T * E, device=self.device)
-            self._etr_buf = torch.empty(T * E, device=self.device)
+        if cat:
+            n_act = self.act_space.n
+            # actions(int64) | states | logits | values | rewards | dones |
+            # boot | moments, in floats
+            n_out = T * E * (2 + D + n_act + 3) + E + 5
+            run, bounds = ext.rollout_run_cat, ()
+        else:
+            n_act = self.act_space.shape[0]
+            n_out = T * E * (D + 3 * n_act + 3) + E + 5
+            run, bounds = ext.rollout_run, self._act_bounds()
+        out = self._rollout_outputs(n_out)
         self._v3_acts_valid = False  # fused kernel does not record acts
         (states, pdflats, actions, values, rewards, dones, boot_v,
-         moments) = ext.rollout_run_cat(
-            blob, offsets, dims,
-            1 if c.ACTIVATION == "tanh" else 0,
+         moments) = run(
+            blob, offsets, dims, self._act_code,
             env.blob, env.rank_eff, env.horizons_i32,
-            float(env.NOISE), float(eps),
-            env.x, env.t, self.epr, T, K, seed, self._rollout_out, 0,
+            float(env.NOISE), *bounds, float(eps),
+            env.x, env.t, self.epr, T, n_act, seed, out, 0,
         )
         self.obs = env.x  # updated in place by the kernel
         return self._finish_hip_rollout(
@@ -509,24 +532,29 @@ class DPPOEngine:
 
     def _finish_hip_rollout(self, states, pdflats, actions, values, rewards,
                             dones, boot_v, moments, eps):
-        c, E = self.cfg, self.cfg.NUM_ENVS
-        T = c.MAX_EPOCH_STEPS
+        c = self.cfg
         adv, etr = gae_advantages(
             rewards, values, dones, boot_v,
             c.GAMMA, c.LAM, whiten=True, eps=c.ADV_EPS,
             policy=c.USE_HIP_KERNELS,
             adv_out=self._adv_buf, etr_out=self._etr_buf,
         )
-        obs_dim = self.obs_space.shape[0]
-        P = self.pi.pdtype.param_shape()[0]
+        return self._make_batch(
+            states, actions, adv, etr, pdflats, values, moments, eps)
+
+    def _make_batch(self, states, actions, adv, etr, pdflats, values,
+                    moments, eps):
+        """(RolloutBatch, info) from the rollout's (T, E, ...) tensors and
+        its five episode-reward moments."""
+        B = states.shape[0] * states.shape[1]
         batch = RolloutBatch(
-            states=states.reshape(T * E, obs_dim),
-            # [T*E, A] float (Box) or [T*E] int64 (Discrete)
-            actions=actions.reshape(T * E, *actions.shape[2:]),
-            adv=adv.reshape(T * E),
-            etr=etr.reshape(T * E),
-            oldflat=pdflats.reshape(T * E, P),
-            oldv=values.reshape(T * E),
+            states=states.reshape(B, states.shape[2]),
+            # [T*E, A] float/int64 vectors or [T*E] int64 (Discrete)
+            actions=actions.reshape(B, *actions.shape[2:]),
+            adv=adv.reshape(B),
+            etr=etr.reshape(B),
+            oldflat=pdflats.reshape(B, pdflats.shape[2]),
+            oldv=values.reshape(B),
             cur_lr=self.current_lr_mul(),
             ep_count=moments[0], ep_sum=moments[1], ep_sumsq=moments[2],
             ep_min=moments[3], ep_max=moments[4],
@@ -534,17 +562,80 @@ class DPPOEngine:
         )
         return batch, {"exploration_rate": eps}
 
-    def _wt_bufs(self):
-        """Persistent [in][out] transposed hidden-layer weight buffers."""
-        shapes = tuple(
-            (lay.weight.shape[1], lay.weight.shape[0]) for lay in self.pi.hidden
-        )
-        if getattr(self, "_wt_key", None) != shapes:
-            self._wt = [
-                torch.empty(sh, device=self.device) for sh in shapes
-            ]
-            self._wt_key = shapes
-        return self._wt
+    def _episode_moments(self, moments, r, done, donef) -> None:
+        """Episode-reward bookkeeping for one env step (Worker.py:57-65),
+        device-side and in place (capture-safe, no host round trip): adds
+        the step rewards to epr, folds the episodes that just ended (`done`,
+        `donef` its float form) into the five moments (count, sum, sum of
+        squares, min, max) and resets their epr."""
+        ep_count, ep_sum, ep_sumsq, ep_min, ep_max = moments
+        epr = self.epr
+        epr += r.float()
+        ep_count += donef.sum()
+        ep_sum += (epr * donef).sum()
+        ep_sumsq += (epr.square() * donef).sum()
+        ep_min.copy_(torch.minimum(ep_min, torch.where(
+            done, epr, torch.full_like(epr, math.inf)).min()))
+        ep_max.copy_(torch.maximum(ep_max, torch.where(
+            done, epr, torch.full_like(epr, -math.inf)).max()))
+        epr *= 1.0 - donef
+
+    def _heads_pad(self) -> bool:
+        """Padded transposed heads [H][P+2] (v at column P, a zero-weight
+        pad column after it): N = P+2 a multiple of 4 routes the heads GEMM
+        through the glds kernel (wt_layout 0, heads mode 2) instead of the
+        pipe kernel; DPPO_HEADS_PAD=0 keeps the pipe kernel."""
+        P = self.pi.pdtype.param_shape()[0]
+        return (P + 2) % 4 == 0 and os.environ.get("DPPO_HEADS_PAD") != "0"
+
+    @torch.no_grad()
+    def _stage_weights(self, fwd: bool = True, dgrad: bool = False) -> dict:
+        """Stage the current parameters into the persistent operand
+        buffers of the MFMA kernels (copy_ only: capture-safe; the zero
+        padding is written once, at allocation).  `fwd`: the forward's
+        operands — transposed hidden weights `wt` and the heads, which
+        `heads_pad` says are the padded and transposed `whT_pad`/`bh_pad`
+        (see _heads_pad) or else the concatenated [Wp; Wv] `wh`/`bh`.
+        `dgrad`: `Wh_pad`, [Wp; Wv] row-padded to gh's float4 row stride
+        (zero rows: the gh pad columns multiply them and contribute
+        nothing), for the per-layer backward."""
+        pi = self.pi
+        P, HL = pi.pi.weight.shape
+        if self._mw is None:
+            dev = self.device
+            self._mw = dict(
+                wt=[torch.empty(lay.weight.shape[1], lay.weight.shape[0],
+                                device=dev) for lay in pi.hidden],
+                wh=torch.empty(P + 1, HL, device=dev),
+                bh=torch.empty(P + 1, device=dev),
+                whT_pad=torch.zeros(HL, P + 2, device=dev),
+                bh_pad=torch.zeros(P + 2, device=dev),
+                Wh_pad=torch.zeros((P + 1 + 3) & ~3, HL, device=dev),
+                heads_pad=False,
+            )
+        mw = self._mw
+        heads = ((pi.pi.weight, pi.pi.bias, slice(0, P)),
+                 (pi.vf.weight, pi.vf.bias, slice(P, P + 1)))
+        if fwd:
+            # hidden weights go in PRE-TRANSPOSED ([in][out], wt_layout 0):
+            # layout-0 staging measured -16% on the big-K layer vs staging
+            # the torch [out][in] layout transposed in LDS
+            for wt, lay in zip(mw["wt"], pi.hidden):
+                wt.copy_(lay.weight.t())
+            mw["heads_pad"] = self._heads_pad()
+            if mw["heads_pad"]:
+                for w, b, rows in heads:
+                    mw["whT_pad"][:, rows].copy_(w.t())
+                    mw["bh_pad"][rows].copy_(b)
+            else:
+                for w, b, rows in heads:
+                    mw["wh"][rows].copy_(w)
+                    mw["bh"][rows].copy_(b)
+        if dgrad:
+            for w, _, rows in heads:
+                mw["Wh_pad"][rows].copy_(w)
+        self._wh_pad_staged = dgrad
+        return mw
 
     def _v3_buffers(self):
         """Persistent device buffers for the per-step GEMM rollout."""
@@ -555,7 +646,7 @@ class DPPOEngine:
         P = 2 * A
         H = tuple(c.HIDDEN_SIZES)
         key = (E, T, D, A, H)
-        if getattr(self, "_v3_key", None) == key:
+        if self._v3_key == key:
             return self._v3
         dev = self.device
         r = env.rank_eff
@@ -571,16 +662,6 @@ class DPPOEngine:
             h=[torch.empty(E, hh, device=dev) for hh in H],
             bz_r=torch.zeros(r, device=dev),
             bz_D=torch.zeros(D, device=dev),
-            wh=torch.empty(P + 1, H[-1], device=dev),
-            bh=torch.empty(P + 1, device=dev),
-            # padded transposed heads weights: N = P+2 (%4 == 0 when
-            # P%4 == 2) routes the heads GEMM through the glds kernel
-            # (wt_layout 0, heads mode 2: v at col N-2, col N-1 is the
-            # zero-weight pad) instead of the pipe kernel
-            whT_pad=(torch.zeros(H[-1], P + 2, device=dev)
-                     if (P + 2) % 4 == 0
-                     and os.environ.get("DPPO_HEADS_PAD") != "0" else None),
-            bh_pad=torch.zeros(P + 2, device=dev),
             pd_scratch=torch.empty(E, P, device=dev),
             seed_dev=torch.zeros(1, dtype=torch.int64, device=dev),
             eps_dev=torch.zeros(1, dtype=torch.float32, device=dev),
@@ -629,7 +710,7 @@ class DPPOEngine:
         the variables it depends on."""
         key = tuple(os.environ.get(k) for k in (
             "DPPO_FWD_FUSED", "DPPO_HEADS_PAD", "DPPO_GEMM_GLDS"))
-        cached = getattr(self, "_fwd_fused_cache", None)
+        cached = self._fwd_fused_cache
         if cached is not None and cached[0] == key:
             return cached[1]
         on = self._resolve_fwd_fused(
@@ -645,7 +726,7 @@ class DPPOEngine:
         if mode == "0":
             return False
         c = self.cfg
-        if self._act_kind != "box" or c.DTYPE != "float32":
+        if not self._hip_path("box"):
             return False
         if c.ACTIVATION not in ("tanh", "relu"):
             return False
@@ -662,10 +743,17 @@ class DPPOEngine:
     def _count_fwd_fused(self, use: str) -> None:
         """Launch counter per use ('rollout', 'boot', 'update'): lets tests
         assert which path ran."""
-        cnt = getattr(self, "fwd_fused_launches", None)
-        if cnt is None:
-            cnt = self.fwd_fused_launches = {}
+        cnt = self.fwd_fused_launches
         cnt[use] = cnt.get(use, 0) + 1
+
+    def _acts_views(self, acts: torch.Tensor, B: int):
+        """Per-layer [B, H_l] views of an activation blob laid out
+        [B*H1 | B*H2 | ...] (what mlp_bwd_rows and the dW GEMMs read)."""
+        views, off = [], 0
+        for hh in self.cfg.HIDDEN_SIZES:
+            views.append(acts.narrow(0, off, B * hh).view(B, hh))
+            off += B * hh
+        return views
 
     def _v3_body(self, states, pdflats, actions, values, rewards, dones,
                  boot_v):
@@ -677,48 +765,31 @@ class DPPOEngine:
         ext = hip_ext()
         c, env, v3 = self.cfg, self.env, self._v3
         E, T = c.NUM_ENVS, c.MAX_EPOCH_STEPS
-        D = self.obs_space.shape[0]
-        A = self.act_space.shape[0]
-        P = 2 * A
-        act_code = 1 if c.ACTIVATION == "tanh" else 0
-        low = float(self.act_space.low.flat[0])
-        high = float(self.act_space.high.flat[0])
+        act_code = self._act_code
+        low, high = self._act_bounds()
         n_h = len(c.HIDDEN_SIZES)
-        wh, bh = v3["wh"], v3["bh"]
-        wh[:P].copy_(self.pi.pi.weight.detach())
-        wh[P:].copy_(self.pi.vf.weight.detach())
-        bh[:P].copy_(self.pi.pi.bias.detach())
-        bh[P:].copy_(self.pi.vf.bias.detach())
-        whT_pad = v3.get("whT_pad")
-        if whT_pad is not None:
-            whT_pad[:, :P + 1].copy_(wh.t())
-            v3["bh_pad"][:P + 1].copy_(bh)
-        wts = self._wt_bufs()
-        for l, lay in enumerate(self.pi.hidden):
-            wts[l].copy_(lay.weight.detach().t())
+        mw = self._stage_weights()
+        wts, wh, bh = mw["wt"], mw["wh"], mw["bh"]
+        whT_pad, bh_pad = mw["whT_pad"], mw["bh_pad"]
+        heads_pad = mw["heads_pad"]
         v3["epr_before"].copy_(self.epr)
         states[0].reshape(-1).copy_(env.x.reshape(-1))
         # whole-batch activation views in the update acts-blob layout;
         # rollout step st writes rows [st*E, (st+1)*E) of each layer
-        hs = c.HIDDEN_SIZES
-        B = T * E
-        acts_views, off = [], 0
-        for hh in hs:
-            acts_views.append(v3["acts"].narrow(0, off, B * hh).view(B, hh))
-            off += B * hh
+        acts_views = self._acts_views(v3["acts"], T * E)
         fused = self._env_fused()
         fold = fused and self._xv_fold() and v3["xvp"] is not None
         no_fold = (v3["empty"], v3["empty"])
         # one launch for L1 + L2 + heads + sampling (bitwise equal to the
         # per-layer chain + rollout_sample; see mlp_fwd_fused_kernel)
-        fwd_fused = whT_pad is not None and self._fwd_fused()
+        fwd_fused = heads_pad and self._fwd_fused()
         hb = [lay.bias.detach() for lay in self.pi.hidden]
         for st in range(T):
             xin = states[st]
             h = xin
             if fwd_fused:
                 ext.mlp_fwd_fused(
-                    xin, wts[0], hb[0], wts[1], hb[1], whT_pad, v3["bh_pad"],
+                    xin, wts[0], hb[0], wts[1], hb[1], whT_pad, bh_pad,
                     act_code, acts_views[0].narrow(0, st * E, E),
                     acts_views[1].narrow(0, st * E, E), pdflats[st],
                     values[st], actions[st], v3["xva"], v3["seed_dev"],
@@ -730,8 +801,8 @@ class DPPOEngine:
                     ext.gemm_fwd(h, wts[l], hb[l], act_code, 0,
                                  hl, hl, hl, 0, 0, 0)
                     h = hl
-                if whT_pad is not None:
-                    ext.gemm_fwd(h, whT_pad, v3["bh_pad"], 2, 2, pdflats[st],
+                if heads_pad:
+                    ext.gemm_fwd(h, whT_pad, bh_pad, 2, 2, pdflats[st],
                                  values[st], pdflats[st], 0, 0, 0)
                 else:
                     ext.gemm_fwd(h, wh, bh, 2, 1, pdflats[st], values[st],
@@ -776,7 +847,7 @@ class DPPOEngine:
         h = env.x
         if fwd_fused:
             ext.mlp_fwd_fused(
-                h, wts[0], hb[0], wts[1], hb[1], whT_pad, v3["bh_pad"],
+                h, wts[0], hb[0], wts[1], hb[1], whT_pad, bh_pad,
                 act_code, v3["h"][0], v3["h"][1], v3["pd_scratch"], boot_v,
                 v3["empty"], v3["empty"], v3["seed_dev"], v3["eps_dev"], 0,
                 0, 0.0, 0.0)
@@ -787,8 +858,8 @@ class DPPOEngine:
             ext.gemm_fwd(h, wts[l], hb[l], act_code, 0,
                          hl, hl, hl, 0, 0, 0)
             h = hl
-        if whT_pad is not None:
-            ext.gemm_fwd(h, whT_pad, v3["bh_pad"], 2, 2, v3["pd_scratch"],
+        if heads_pad:
+            ext.gemm_fwd(h, whT_pad, bh_pad, 2, 2, v3["pd_scratch"],
                          boot_v, v3["pd_scratch"], 0, 0, 0)
         else:
             ext.gemm_fwd(h, wh, bh, 2, 1, v3["pd_scratch"], boot_v,
@@ -803,21 +874,11 @@ class DPPOEngine:
         T = c.MAX_EPOCH_STEPS
         eps = self.exploration_rate()
         env = self.env
-        self._rollout_counter = getattr(self, "_rollout_counter", 0) + 1
-        seed = (
-            c.SEED * 1_000_003
-            + self.comm.rank * 7_919
-            + self._rollout_counter * 104_729
-        ) & 0x7FFFFFFFFFFFFFFF
+        seed = self._next_rollout_seed()
         A = self.act_space.shape[0]
         D = self.obs_space.shape[0]
         P = 2 * A
-        n_out = T * E * (D + 3 * A + 3) + E + 5
-        if getattr(self, "_rollout_out", None) is None or                 self._rollout_out.numel() != n_out:
-            self._rollout_out = torch.empty(n_out, device=self.device)
-            self._adv_buf = torch.empty(T * E, device=self.device)
-            self._etr_buf = torch.empty(T * E, device=self.device)
-        out = self._rollout_out
+        out = self._rollout_outputs(T * E * (D + 3 * A + 3) + E + 5)
         o = 0
 
         def take(shape):
@@ -843,27 +904,19 @@ class DPPOEngine:
         # unlike the update graph, the rollout graph contains NO
         # collectives — capture is safe on every rank
         graph_ok = c.USE_GRAPHS
-        if not graph_ok or getattr(self, "_v3_graph_failed", False):
+        if not graph_ok or self._v3_graph_failed:
             moments = self._v3_body(*args)
-        elif getattr(self, "_v3_graph", None) is None:
+        elif self._v3_graph is None:
+            def capture_body():
+                self._v3_moments = self._v3_body(*args)
+
             try:
-                # warmup on a side stream, then restore env/episode state
-                # so capture replays from the true starting state
-                snap = (env.x.clone(), env.t.clone(), self.epr.clone())
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    self._v3_body(*args)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                env.x.copy_(snap[0])
-                env.t.copy_(snap[1])
-                self.epr.copy_(snap[2])
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._v3_moments = self._v3_body(*args)
-                self._v3_graph = g
-                g.replay()
+                # the warmup runs the rollout for real: env/episode state
+                # is restored so capture replays from the true start
+                (self._v3_graph,) = warm_and_capture(
+                    (env.x, env.t, self.epr),
+                    lambda: self._v3_body(*args), [capture_body])
+                self._v3_graph.replay()
                 moments = self._v3_moments
             except Exception as exc:  # noqa: BLE001 — capture support varies
                 self._warn_once(
@@ -893,7 +946,7 @@ class DPPOEngine:
         A = self.act_space.shape[0]
         P = self.pi.pdtype.param_shape()[0]
         key = (T, E, D, A)
-        if getattr(self, "_wr_key", None) == key:
+        if self._wr_key == key:
             return self._wr
         dev = self.device
         self._wr = dict(
@@ -922,14 +975,9 @@ class DPPOEngine:
         c, env = self.cfg, self.env
         T, E = c.MAX_EPOCH_STEPS, c.NUM_ENVS
         eps = b["eps_dev"]
-        (ep_count, ep_sum, ep_sumsq, ep_min, ep_max) = b["eps_moments"]
-        ep_count.zero_()
-        ep_sum.zero_()
-        ep_sumsq.zero_()
-        ep_min.fill_(math.inf)
-        ep_max.fill_(-math.inf)
-        ninf = -float("inf")
-        pinf = float("inf")
+        moments = b["eps_moments"]
+        for m, start in zip(moments, (0.0, 0.0, 0.0, math.inf, -math.inf)):
+            m.fill_(start)
         env.x = b["x_env"]
         env.t = b["t_env"]
         obs = b["x_env"]
@@ -960,15 +1008,7 @@ class DPPOEngine:
             b["rewards"][t].copy_(r.float())
             donef = done.float()
             b["dones"][t].copy_(donef)
-            self.epr += r.float()
-            ep_count += donef.sum()
-            ep_sum += (self.epr * donef).sum()
-            ep_sumsq += (self.epr.square() * donef).sum()
-            ep_min.copy_(torch.minimum(
-                ep_min, torch.where(done, self.epr, torch.full_like(self.epr, pinf)).min()))
-            ep_max.copy_(torch.maximum(
-                ep_max, torch.where(done, self.epr, torch.full_like(self.epr, ninf)).max()))
-            self.epr *= 1.0 - donef
+            self._episode_moments(moments, r, done, donef)
         boot_v, _ = wide.forward(obs)
         b["boot_v"].copy_(boot_v)
         # fold live env state back into the stable buffers
@@ -983,32 +1023,22 @@ class DPPOEngine:
         ~450 small launches per round otherwise leave the GPU idle
         between kernels).  RNG (action sampling, eps overlay, env noise)
         is graph-captured via registered generator states."""
-        c, E = self.cfg, self.cfg.NUM_ENVS
-        T = c.MAX_EPOCH_STEPS
+        c = self.cfg
         eps = self.exploration_rate()
         b = self._wide_rollout_buffers()
         b["eps_dev"].fill_(eps)
-        if getattr(self, "_wr_graph", None) is None:
+        if self._wr_graph is None:
             b["x_env"].copy_(self.env.x)
             b["t_env"].copy_(self.env.t)
             try:
                 self._wide().refresh_weights()
-                # warmup on a side stream, then restore env/episode state
-                snap = (b["x_env"].clone(), b["t_env"].clone(),
-                        self.epr.clone())
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    self._wide_rollout_body(b)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                b["x_env"].copy_(snap[0])
-                b["t_env"].copy_(snap[1])
-                self.epr.copy_(snap[2])
-                g = torch.cuda.CUDAGraph()
-                g.register_generator_state(self.env._noise_gen)
-                with torch.cuda.graph(g):
-                    self._wide_rollout_body(b)
+                # the warmup runs the rollout for real: env/episode state
+                # is restored before the capture
+                (g,) = warm_and_capture(
+                    (b["x_env"], b["t_env"], self.epr),
+                    lambda: self._wide_rollout_body(b),
+                    [lambda: self._wide_rollout_body(b)],
+                    generators=[self.env._noise_gen])
                 self._wr_graph = g
                 g.replay()
             except Exception as exc:  # noqa: BLE001 — capture support varies
@@ -1034,25 +1064,12 @@ class DPPOEngine:
             c.GAMMA, c.LAM, whiten=True, eps=c.ADV_EPS,
             policy=c.USE_HIP_KERNELS,
         )
-        P = self.pi.pdtype.param_shape()[0]
-        obs_dim = self.obs_space.shape[0]
-        m = b["eps_moments"]
-        batch = RolloutBatch(
-            states=b["states"].reshape(T * E, obs_dim),
-            actions=b["actions"].reshape(T * E, self.act_space.shape[0]),
-            adv=adv.reshape(T * E),
-            etr=etr.reshape(T * E),
-            oldflat=b["pdflats"].reshape(T * E, P),
-            oldv=b["values"].reshape(T * E),
-            cur_lr=self.current_lr_mul(),
-            ep_count=m[0], ep_sum=m[1], ep_sumsq=m[2],
-            ep_min=m[3], ep_max=m[4],
-            valid=float(m[0]) > 0,
-        )
-        return batch, {"exploration_rate": eps}
+        return self._make_batch(
+            b["states"], b["actions"], adv, etr, b["pdflats"], b["values"],
+            b["eps_moments"], eps)
 
     def _weights_need_refresh_for_rollout(self) -> bool:
-        w = getattr(self, "_wide_path", None)
+        w = self._wide_path
         return w is not None and w._weights_dirty
 
     @torch.no_grad()
@@ -1093,13 +1110,8 @@ class DPPOEngine:
         # device-side episode-reward moments: the reference appends python
         # floats per done (Worker.py:62-65); here masked tensor ops keep
         # the whole loop sync-free (no host round trip per step).
-        ep_count = torch.zeros((), device=dev)
-        ep_sum = torch.zeros((), device=dev)
-        ep_sumsq = torch.zeros((), device=dev)
-        ep_min = torch.full((), math.inf, device=dev)
-        ep_max = torch.full((), -math.inf, device=dev)
-        ninf = torch.full((), -math.inf, device=dev)
-        pinf = torch.full((), math.inf, device=dev)
+        moments = [torch.full((), start, device=dev)
+                   for start in (0.0, 0.0, 0.0, math.inf, -math.inf)]
 
         obs = self.obs
         for t in range(T):
@@ -1112,14 +1124,7 @@ class DPPOEngine:
             rewards[t] = r.float()
             donef = done.float()
             dones[t] = donef
-            # episode-reward bookkeeping (Worker.py:57-65), device-side
-            self.epr += r.float()
-            ep_count += donef.sum()
-            ep_sum += (self.epr * donef).sum()
-            ep_sumsq += (self.epr.square() * donef).sum()
-            ep_min = torch.minimum(ep_min, torch.where(done, self.epr, pinf).min())
-            ep_max = torch.maximum(ep_max, torch.where(done, self.epr, ninf).max())
-            self.epr *= 1.0 - donef
+            self._episode_moments(moments, r, done, donef)
         self.obs = obs
 
         with torch.no_grad():
@@ -1130,19 +1135,8 @@ class DPPOEngine:
             policy=c.USE_HIP_KERNELS,
         )
 
-        batch = RolloutBatch(
-            states=states.reshape(T * E, obs_dim),
-            actions=actions.reshape(T * E, *actions.shape[2:]),
-            adv=adv.reshape(T * E).to(self.dtype),
-            etr=etr.reshape(T * E).to(self.dtype),
-            oldflat=pdflats.reshape(T * E, P),
-            oldv=values.reshape(T * E).to(self.dtype),
-            cur_lr=self.current_lr_mul(),
-            ep_count=ep_count, ep_sum=ep_sum, ep_sumsq=ep_sumsq,
-            ep_min=ep_min, ep_max=ep_max,
-            valid=float(ep_count) > 0,  # the rollout's single host sync
-        )
-        return batch, {"exploration_rate": eps}
+        return self._make_batch(
+            states, actions, adv, etr, pdflats, values, moments, eps)
 
     def collect(self) -> RolloutBatch:
         """Rollout with the push guard: retry (discarding) until at least
@@ -1285,12 +1279,12 @@ class DPPOEngine:
         B = batch.states.shape[0]
         fuse = self._can_fuse_update()
         clip = self.cfg.CLIP_PARAM * l_mul
-        if fuse and getattr(self, "_clip_dev", None) is not None:
+        if fuse and self._clip_dev is not None:
             self._clip_dev.fill_(clip)
         if (fuse and self.cfg.USE_GRAPHS
                 and (not self.comm.distributed
                      or os.environ.get("DPPO_GRAPH_DIST") == "1")
-                and not getattr(self, "_mb_graph_failed", False)):
+                and not self._mb_graph_failed):
             # Only CAPTURE failures fall through to the uncaptured loop
             # (capture is state-safe: warmup is snapshot/restored and a
             # capture records, not executes).  A failure during replay or
@@ -1300,7 +1294,7 @@ class DPPOEngine:
             if self._update_minibatched_graphed(batch, l_mul):
                 return
         use_ck = fuse and self._can_chunk_kernel(min(mb, B))
-        if use_ck:
+        if fuse:
             self.optimizer.lr_dev.fill_(self.cfg.LEARNING_RATE * l_mul)
         for _ in range(self.cfg.UPDATE_STEPS):
             for o in range(0, B, mb):
@@ -1308,29 +1302,13 @@ class DPPOEngine:
                 if use_ck:
                     self._chunk_kernel_step(batch, o, n, clip)
                     continue
-                sub = RolloutBatch(
-                    states=batch.states.narrow(0, o, n),
-                    actions=batch.actions.narrow(0, o, n),
-                    adv=batch.adv.narrow(0, o, n),
-                    etr=batch.etr.narrow(0, o, n),
-                    oldflat=batch.oldflat.narrow(0, o, n),
-                    oldv=batch.oldv.narrow(0, o, n),
-                    cur_lr=batch.cur_lr,
-                    ep_count=batch.ep_count, ep_sum=batch.ep_sum,
-                    ep_sumsq=batch.ep_sumsq, ep_min=batch.ep_min,
-                    ep_max=batch.ep_max, valid=batch.valid,
-                )
-                self.flat_pi.zero_grad()
+                sub = batch.narrow(o, n)
                 if fuse:
-                    acts, a_views, v, pdflat = self._fused_forward(sub.states)
-                    self._fused_backward(
-                        sub.states, acts, a_views, v, pdflat,
-                        sub.oldflat, sub.oldv, sub.actions,
-                        sub.adv, sub.etr, clip,
-                    )
-                else:
-                    losses = self._losses(sub, l_mul)
-                    losses["total_loss"].backward()
+                    self._fused_step(sub, clip)
+                    continue
+                self.flat_pi.zero_grad()
+                losses = self._losses(sub, l_mul)
+                losses["total_loss"].backward()
                 self.comm.allreduce_mean_(self.flat_pi.flat_grad)
                 self.optimizer.step()
 
@@ -1357,16 +1335,15 @@ class DPPOEngine:
         n_full = B // mb
         tail = B - n_full * mb
         clip = c.CLIP_PARAM * l_mul
-        if getattr(self, "_clip_dev", None) is None:
+        if self._clip_dev is None:
             self._clip_dev = torch.tensor([clip], device=self.device)
         else:
             self._clip_dev.fill_(clip)
-        opt = self.optimizer
-        opt.lr_dev.fill_(c.LEARNING_RATE * l_mul)
+        self.optimizer.lr_dev.fill_(c.LEARNING_RATE * l_mul)
         key = (batch.states.data_ptr(), batch.actions.data_ptr(),
                batch.adv.data_ptr(), batch.etr.data_ptr(),
                batch.oldflat.data_ptr(), batch.oldv.data_ptr(), B, mb)
-        if getattr(self, "_mb_graphs", None) is None or self._mb_key != key:
+        if self._mb_graphs is None or self._mb_key != key:
             try:
                 self._mb_capture(batch, key, n_full)
             except Exception as exc:  # noqa: BLE001 — capture support varies
@@ -1395,52 +1372,29 @@ class DPPOEngine:
         if self._can_chunk_kernel(n):
             self._chunk_kernel_step(batch, o, n, 0.0)  # clip via _clip_dev
             return
-        s = batch.states.narrow(0, o, n)
-        acts, a_views, v, pdflat = self._fused_forward(s)
-        self.flat_pi.zero_grad()
-        self._fused_backward(
-            s, acts, a_views, v, pdflat,
-            batch.oldflat.narrow(0, o, n), batch.oldv.narrow(0, o, n),
-            batch.actions.narrow(0, o, n), batch.adv.narrow(0, o, n),
-            batch.etr.narrow(0, o, n), 0.0,  # clip read from _clip_dev
-        )
-        self.comm.allreduce_mean_(self.flat_pi.flat_grad)
-        self.optimizer.step_captured()
+        self._fused_step(batch.narrow(o, n), 0.0)  # clip via _clip_dev
+
+    def _train_state(self):
+        """What an update step mutates: parameters, Adam moments, step
+        count.  Graph warm-ups execute real steps and restore these."""
+        opt = self.optimizer
+        return (self.flat_pi.flat_param, opt.exp_avg, opt.exp_avg_sq,
+                opt.step_dev)
 
     def _mb_capture(self, batch: RolloutBatch, key, n_full: int) -> None:
         mb = self.cfg.MINIBATCH_SIZE
-        opt = self.optimizer
-        # warmup executes real steps (lazy inits, allocator) — snapshot
-        # and restore the full optimizer+param state around it
-        snap = (
-            self.flat_pi.flat_param.detach().clone(),
-            opt.exp_avg.clone(), opt.exp_avg_sq.clone(),
-            opt.step_dev.clone(),
-        )
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for ci in range(min(2, n_full)):
-                    self._mb_chunk_step(batch, ci * mb, mb)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-        finally:
-            with torch.no_grad():
-                self.flat_pi.flat_param.copy_(snap[0])
-                opt.exp_avg.copy_(snap[1])
-                opt.exp_avg_sq.copy_(snap[2])
-                opt.step_dev.copy_(snap[3])
-        pool = torch.cuda.graph_pool_handle()
-        graphs = []
-        for s0 in range(0, n_full, self._MB_SEG):
-            s1 = min(n_full, s0 + self._MB_SEG)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
-                for ci in range(s0, s1):
-                    self._mb_chunk_step(batch, ci * mb, mb)
-            graphs.append(g)
-        self._mb_graphs = graphs
+
+        def chunks(lo, hi):
+            for ci in range(lo, hi):
+                self._mb_chunk_step(batch, ci * mb, mb)
+
+        # the warmup (lazy inits, allocator) is two chunks; the epoch is
+        # captured in segments of _MB_SEG chunks sharing one pool
+        self._mb_graphs = warm_and_capture(
+            self._train_state(), lambda: chunks(0, min(2, n_full)),
+            [lambda s0=s0: chunks(s0, min(n_full, s0 + self._MB_SEG))
+             for s0 in range(0, n_full, self._MB_SEG)],
+            pool=torch.cuda.graph_pool_handle())
         self._mb_key = key
 
     # Max batch routed to the fused chunk-step kernel (mlp_train.hip):
@@ -1459,13 +1413,11 @@ class DPPOEngine:
         """Eligibility for the fused single-kernel chunk step
         (ops/hip/mlp_train.hip): the whole fwd + PPO grad + bwd + dW +
         Adam for one (mini)batch chunk in two kernel launches."""
-        from .ops import use_hip, hip_ext
+        from .ops import hip_ext
         from .ops.adam import FusedFlatAdam
 
         c = self.cfg
-        if self._act_kind != "box" or c.DTYPE != "float32":
-            return False
-        if not use_hip(self.device, c.USE_HIP_KERNELS):
+        if not self._hip_path("box"):
             return False
         if B > self.CHUNK_KERNEL_MAX_B:
             return False
@@ -1479,7 +1431,7 @@ class DPPOEngine:
 
     def _chunk_scratch(self) -> torch.Tensor:
         """Per-block gradient slab scratch (<=256 blocks x padded P)."""
-        if getattr(self, "_chunk_slabs", None) is None:
+        if self._chunk_slabs is None:
             ppad = (self.flat_pi.flat_param.numel() + 3) & ~3
             self._chunk_slabs = torch.zeros(
                 256 * ppad, device=self.device, dtype=torch.float32)
@@ -1504,7 +1456,7 @@ class DPPOEngine:
             batch.states.narrow(0, o, n), batch.actions.narrow(0, o, n),
             batch.adv.narrow(0, o, n), batch.etr.narrow(0, o, n),
             batch.oldflat.narrow(0, o, n), batch.oldv.narrow(0, o, n),
-            offsets, dims, 1 if c.ACTIVATION == "tanh" else 0,
+            offsets, dims, self._act_code,
             self._clip_dev_or_empty(), clip, c.ENTCOEFF, c.VCOEFF,
             self._chunk_scratch(), opt.exp_avg, opt.exp_avg_sq,
             opt.step_dev, opt.lr_dev, opt.coef,
@@ -1515,10 +1467,9 @@ class DPPOEngine:
             opt.step_captured()
 
     def _clip_dev_or_empty(self) -> torch.Tensor:
-        t = getattr(self, "_clip_dev", None)
-        if t is None:
-            t = torch.empty(0, device=self.device)
-        return t
+        if self._clip_dev is None:
+            return torch.empty(0, device=self.device)
+        return self._clip_dev
 
     def _update_graphed(self, batch: RolloutBatch, l_mul: float) -> None:
         """hipGraph-captured update: the whole UPDATE_STEPS pipeline
@@ -1530,42 +1481,27 @@ class DPPOEngine:
         Any capture failure falls back to the uncaptured fused path."""
         clip = self.cfg.CLIP_PARAM * l_mul
         lr = self.cfg.LEARNING_RATE * l_mul
-        if getattr(self, "_graph_failed", False):
+        if self._graph_failed:
             self._update_fused(batch, l_mul)
             return
-        if (getattr(self, "_upd_graph", None) is not None
-                and getattr(self, "_upd_graph_skip", None)
-                != bool(getattr(self, "_v3_acts_valid", False))):
+        if (self._upd_graph is not None
+                and self._upd_graph_skip != self._v3_acts_valid):
             self._upd_graph = None  # skip-first structure changed
-        if getattr(self, "_upd_graph", None) is None:
+        if self._upd_graph is None:
+            def warmup():
+                for _ in range(2):
+                    self._update_body(batch)
+
             try:
                 self._clip_dev = torch.tensor([clip], device=self.device)
-                opt = self.optimizer
-                opt.lr_dev.fill_(lr)
-                # snapshot optimizer+param state: warmup executes real steps
-                snap = (
-                    self.flat_pi.flat_param.detach().clone(),
-                    opt.exp_avg.clone(), opt.exp_avg_sq.clone(),
-                    opt.step_dev.clone(),
-                )
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        self._update_body(batch)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                with torch.no_grad():
-                    self.flat_pi.flat_param.copy_(snap[0])
-                    opt.exp_avg.copy_(snap[1])
-                    opt.exp_avg_sq.copy_(snap[2])
-                    opt.step_dev.copy_(snap[3])
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._update_body(batch)
-                self._upd_graph = g
-                self._upd_graph_skip = bool(
-                    getattr(self, "_v3_acts_valid", False))
+                self.optimizer.lr_dev.fill_(lr)
+                # the warmup executes real steps: optimizer+param state is
+                # restored, also when it raises (the fallback below must
+                # not step the round a second time)
+                (self._upd_graph,) = warm_and_capture(
+                    self._train_state(), warmup,
+                    [lambda: self._update_body(batch)])
+                self._upd_graph_skip = self._v3_acts_valid
             except Exception as exc:  # noqa: BLE001 — capture support varies
                 self._warn_once(
                     "upd_graph",
@@ -1588,45 +1524,45 @@ class DPPOEngine:
             for _ in range(self.cfg.UPDATE_STEPS):
                 self._chunk_kernel_step(batch, 0, B, 0.0)  # clip: _clip_dev
             return
-        skip1 = (bool(getattr(self, "_v3_acts_valid", False))
+        self._fused_steps(batch, 0.0)  # clip read from _clip_dev
+
+    def _fused_steps(self, batch: RolloutBatch, clip: float) -> None:
+        """UPDATE_STEPS full-batch fused steps; step 1 reuses the v3
+        rollout's recorded activations when they are valid."""
+        skip1 = (self._v3_acts_valid
                  and os.environ.get("DPPO_NO_SKIP1") != "1")
         for si in range(self.cfg.UPDATE_STEPS):
-            if si == 0 and skip1:
-                acts, a_views, v, pdflat = self._recorded_acts(batch)
-            else:
-                acts, a_views, v, pdflat = self._fused_forward(batch.states)
-            self.flat_pi.zero_grad()
-            self._fused_backward(
-                batch.states, acts, a_views, v, pdflat,
-                batch.oldflat, batch.oldv, batch.actions,
-                batch.adv, batch.etr, 0.0,  # clip read from _clip_dev
-            )
-            self.comm.allreduce_mean_(self.flat_pi.flat_grad)
-            self.optimizer.step_captured()
+            self._fused_step(batch, clip, recorded=(si == 0 and skip1))
+
+    def _fused_step(self, batch: RolloutBatch, clip: float,
+                    recorded: bool = False) -> None:
+        """One fused gradient step on `batch` (a full batch or a minibatch
+        chunk): MFMA forward (or, `recorded`, the rollout's activations)
+        -> GEMM-shaped backward -> all-reduce -> device-state Adam, lr
+        from lr_dev.  A live _clip_dev overrides `clip` inside the kernels
+        (captured callers pass 0.0), so the step is capture-safe."""
+        acts, a_views, v, pdflat = (
+            self._recorded_acts(batch) if recorded
+            else self._fused_forward(batch.states))
+        self.flat_pi.zero_grad()
+        self._fused_backward(
+            batch.states, acts, a_views, v, pdflat,
+            batch.oldflat, batch.oldv, batch.actions,
+            batch.adv, batch.etr, clip,
+        )
+        self.comm.allreduce_mean_(self.flat_pi.flat_grad)
+        self.optimizer.step_captured()
 
     def _recorded_acts(self, batch: RolloutBatch):
         """(acts, a_views, v, pdflat) from the v3 rollout's recorded
         activation blob — valid only for the FIRST update step of a round
         (parameters unchanged between rollout and step 1); pdflat/v are
         the recorded oldflat/oldv, making the step-1 ratio exactly 1."""
-        v3 = self._v3
-        B = batch.states.shape[0]
-        acts = v3["acts"]
-        a_views, off = [], 0
-        for hh in self.cfg.HIDDEN_SIZES:
-            a_views.append(acts.narrow(0, off, B * hh).view(B, hh))
-            off += B * hh
-        if self._mid_fused_mode():
-            # the mid kernel reads the head weights from the flat buffer
-            self._Wh_pad = None
-            return acts, a_views, batch.oldv, batch.oldflat
-        with torch.no_grad():
-            Wh_cat = torch.cat(
-                [self.pi.pi.weight, self.pi.vf.weight], dim=0).contiguous()
-            ldp = (Wh_cat.shape[0] + 3) & ~3
-            Wh_pad = torch.zeros(ldp, Wh_cat.shape[1], device=self.device)
-            Wh_pad[:Wh_cat.shape[0]] = Wh_cat
-            self._Wh_pad = Wh_pad
+        acts = self._v3["acts"]
+        a_views = self._acts_views(acts, batch.states.shape[0])
+        # no forward runs: only the per-layer backward needs an operand
+        # (the mid kernel reads the head weights from the flat buffer)
+        self._stage_weights(fwd=False, dgrad=not self._mid_fused_mode())
         return acts, a_views, batch.oldv, batch.oldflat
 
     def _fused_forward(self, states: torch.Tensor):
@@ -1634,85 +1570,47 @@ class DPPOEngine:
 
         Returns (acts_blob, a_views, v, pdflat): activations land in one
         contiguous blob laid out [B*H1 | B*H2 | ...] for mlp_bwd_rows.
-        Weight transposes are cheap (<100 KB) and re-done per call since
-        params change every update step."""
+        The weight operands are re-staged per call since params change
+        every update step (<100 KB of copies); the outputs are fresh
+        tensors, which callers may keep."""
         from .ops import hip_ext
 
         ext = hip_ext()
         c = self.cfg
         B = states.shape[0]
-        dims = [self.obs_space.shape[0], *c.HIDDEN_SIZES]
-        n_hidden = len(c.HIDDEN_SIZES)
-        act_code = 1 if c.ACTIVATION == "tanh" else 0
-        with torch.no_grad():
-            # hidden-layer weights go in PRE-TRANSPOSED ([in][out],
-            # wt_layout 0): layout-0 staging measured -16% on the big-K
-            # layer vs staging the torch [out][in] layout transposed in
-            # LDS (layout 1's per-thread scalar column writes).  The
-            # transpose copies are <100 KB and re-done per call since
-            # params change every update step (capture-safe: persistent
-            # buffers + copy_).
-            bs = [lay.bias.detach() for lay in self.pi.hidden]
-            wts = self._wt_bufs()
-            for l, lay in enumerate(self.pi.hidden):
-                wts[l].copy_(lay.weight.detach().t())
-            Wh_cat = torch.cat(
-                [self.pi.pi.weight, self.pi.vf.weight], dim=0
-            ).contiguous()  # [P+1][HL]: heads fwd (layout 1)
-            # dgrad Wt padded to gh's float4 row stride (zero rows: the
-            # gh pad columns multiply them and contribute nothing); the
-            # mid kernel reads the head weights from the flat buffer
-            Wh_pad = None
-            if not self._mid_fused_mode():
-                ldp = (Wh_cat.shape[0] + 3) & ~3
-                Wh_pad = torch.zeros(ldp, Wh_cat.shape[1],
-                                     device=Wh_cat.device)
-                Wh_pad[:Wh_cat.shape[0]] = Wh_cat
-            bh = torch.cat([self.pi.pi.bias, self.pi.vf.bias]).contiguous()
-        total = sum(B * dims[l + 1] for l in range(n_hidden))
-        acts = torch.empty(total, device=states.device, dtype=states.dtype)
-        a_views, o = [], 0
-        for l in range(n_hidden):
-            n = B * dims[l + 1]
-            a_views.append(acts.narrow(0, o, n).view(B, dims[l + 1]))
-            o += n
+        act_code = self._act_code
+        bs = [lay.bias.detach() for lay in self.pi.hidden]
+        # the per-layer backward also wants Wh_pad; the mid kernel reads
+        # the head weights from the flat buffer
+        mw = self._stage_weights(dgrad=not self._mid_fused_mode())
+        wts, whT_pad, bh_pad = mw["wt"], mw["whT_pad"], mw["bh_pad"]
+        acts = torch.empty(B * sum(c.HIDDEN_SIZES), device=states.device,
+                           dtype=states.dtype)
+        a_views = self._acts_views(acts, B)
         P = 2 * self.act_space.shape[0]
         pdflat = torch.empty(B, P, device=states.device, dtype=states.dtype)
         v = torch.empty(B, device=states.device, dtype=states.dtype)
-        if self._fwd_fused():
+        if mw["heads_pad"] and self._fwd_fused():
             # one launch: h1 / h2 are written once for the backward and
             # never read back by the forward
-            with torch.no_grad():
-                WhT_pad = torch.zeros(Wh_cat.shape[1], P + 2,
-                                      device=states.device)
-                WhT_pad[:, :P + 1] = Wh_cat.t()
-                bh2 = torch.zeros(P + 2, device=states.device)
-                bh2[:P + 1] = bh
             empty = states.new_empty(0)
-            ext.mlp_fwd_fused(states, wts[0], bs[0], wts[1], bs[1], WhT_pad,
-                              bh2, act_code, a_views[0], a_views[1], pdflat,
-                              v, empty, empty, empty, empty, 0, 0, 0.0, 0.0)
+            ext.mlp_fwd_fused(states, wts[0], bs[0], wts[1], bs[1], whT_pad,
+                              bh_pad, act_code, a_views[0], a_views[1],
+                              pdflat, v, empty, empty, empty, empty, 0, 0,
+                              0.0, 0.0)
             self._count_fwd_fused("update")
-            self._Wh_pad = Wh_pad
             return acts, a_views, v, pdflat
         x = states
-        for l in range(n_hidden):
+        for l in range(len(wts)):
             ext.gemm_fwd(x, wts[l], bs[l],
                          act_code, 0, a_views[l], a_views[l], a_views[l],
                          0, 0, 0)
             x = a_views[l]
-        if (P + 2) % 4 == 0 and os.environ.get("DPPO_HEADS_PAD") != "0":
-            # padded transposed heads (N=P+2, %4==0): glds kernel with
-            # heads mode 2 instead of the layout-1 pipe kernel
-            WhT_pad = torch.zeros(Wh_cat.shape[1], P + 2,
-                                  device=states.device)
-            WhT_pad[:, :P + 1] = Wh_cat.t()
-            bh2 = torch.zeros(P + 2, device=states.device)
-            bh2[:P + 1] = bh
-            ext.gemm_fwd(x, WhT_pad, bh2, 2, 2, pdflat, v, pdflat, 0, 0, 0)
+        if mw["heads_pad"]:
+            ext.gemm_fwd(x, whT_pad, bh_pad, 2, 2, pdflat, v, pdflat, 0, 0, 0)
         else:
-            ext.gemm_fwd(x, Wh_cat, bh, 2, 1, pdflat, v, pdflat, 1, 0, 0)
-        self._Wh_pad = Wh_pad
+            ext.gemm_fwd(x, mw["wh"], mw["bh"], 2, 1, pdflat, v, pdflat,
+                         1, 0, 0)
         return acts, a_views, v, pdflat
 
     # the DPPO_MID_FUSED default: what profiles/r05_update_mid_fused.txt
@@ -1725,7 +1623,7 @@ class DPPOEngine:
         shape is eligible.  Anything else is an error, not a fall-back.
         Resolved once per engine and value of the variable."""
         env = os.environ.get("DPPO_MID_FUSED", self.MID_FUSED_DEFAULT)
-        cached = getattr(self, "_mid_mode_cache", None)
+        cached = self._mid_mode_cache
         if cached is not None and cached[0] == env:
             return cached[1]
         mode = self._resolve_mid_mode(env)
@@ -1741,7 +1639,7 @@ class DPPOEngine:
             raise ValueError(
                 f"DPPO_MID_FUSED={mode!r}: expected '0' or 'load'")
         c = self.cfg
-        if self._act_kind != "box" or c.DTYPE != "float32":
+        if not self._hip_path("box"):
             return ""
         if c.ACTIVATION not in ("tanh", "relu"):
             return ""
@@ -1766,7 +1664,7 @@ class DPPOEngine:
         ext.mlp_mid_bwd(
             self.flat_pi.flat_param.detach(), offsets, a_views[0], a_views[1],
             pdflat, v, oldflat, oldv, actions, adv, etr,
-            1 if c.ACTIVATION == "tanh" else 0, self._clip_dev_or_empty(),
+            self._act_code, self._clip_dev_or_empty(),
             clip, c.ENTCOEFF, c.VCOEFF, dz1, grad)
         ext.dw_mfma(dz1, states, grad, offsets[0], offsets[1], -1, -1, -1, 0)
         return dz1
@@ -1797,17 +1695,12 @@ class DPPOEngine:
             pdflat, oldflat, v, oldv, actions, adv, etr,
             clip, c.ENTCOEFF, c.VCOEFF, self._clip_dev_or_empty(),
         )
-        # _fused_forward cached the PADDED [Wp; Wv; 0...] — its rows are
-        # the dgrad Wt matching gh's float4-padded row stride
-        Wh_pad = getattr(self, "_Wh_pad", None)
-        if Wh_pad is None or Wh_pad.shape[0] != gh.shape[1]:
-            with torch.no_grad():
-                Wh_cat = torch.cat(
-                    [self.pi.pi.weight, self.pi.vf.weight], dim=0
-                ).contiguous()
-                Wh_pad = torch.zeros(gh.shape[1], Wh_cat.shape[1],
-                                     device=self.device)
-                Wh_pad[:Wh_cat.shape[0]] = Wh_cat
+        # the staged PADDED [Wp; Wv; 0...]: its rows are the dgrad Wt
+        # matching gh's float4-padded row stride.  The forward stages it
+        # unless it ran in the mid-kernel mode
+        if not self._wh_pad_staged:
+            self._stage_weights(fwd=False, dgrad=True)
+        Wh_pad = self._mw["Wh_pad"]
         dz = [None] * n_hidden
         delta, Wt_chain = gh, Wh_pad
         for l in range(n_hidden - 1, -1, -1):
@@ -1831,29 +1724,16 @@ class DPPOEngine:
         clip = self.cfg.CLIP_PARAM * l_mul
         # a live _clip_dev overrides the kernel's clip argument; keep it
         # coherent when falling back from the graphed path
-        if getattr(self, "_clip_dev", None) is not None:
+        if self._clip_dev is not None:
             self._clip_dev.fill_(clip)
+        self.optimizer.lr_dev.fill_(self.cfg.LEARNING_RATE * l_mul)
         B = batch.states.shape[0]
         if self._can_chunk_kernel(B):
-            self.optimizer.lr_dev.fill_(self.cfg.LEARNING_RATE * l_mul)
             for _ in range(self.cfg.UPDATE_STEPS):
                 self._chunk_kernel_step(batch, 0, B, clip)
             return
-        skip1 = (bool(getattr(self, "_v3_acts_valid", False))
-                 and os.environ.get("DPPO_NO_SKIP1") != "1")
-        for si in range(self.cfg.UPDATE_STEPS):
-            if si == 0 and skip1:
-                acts, a_views, v, pdflat = self._recorded_acts(batch)
-            else:
-                acts, a_views, v, pdflat = self._fused_forward(batch.states)
-            self.flat_pi.zero_grad()
-            self._fused_backward(
-                batch.states, acts, a_views, v, pdflat,
-                batch.oldflat, batch.oldv, batch.actions,
-                batch.adv, batch.etr, clip,
-            )
-            self.comm.allreduce_mean_(self.flat_pi.flat_grad)
-            self.optimizer.step()
+        self._fused_steps(batch, clip)
+
     # ------------------------------------------------------------------
     def _curate_batches(self, batch: RolloutBatch,
                         gathered: torch.Tensor) -> RolloutBatch:
@@ -1871,8 +1751,6 @@ class DPPOEngine:
         Every rank executes the identical schedule (gathered stats are
         identical across ranks), so sends and recvs pair deterministically.
         """
-        import dataclasses as _dc
-
         W = self.comm.world_size
         r = self.comm.rank
         valid = gathered[:, 10] > 0.5
@@ -1885,7 +1763,7 @@ class DPPOEngine:
         srcs = [order[i] if i < V else order[i % V] for i in range(W)]
         if all(s == i for i, s in enumerate(srcs)):
             return batch
-        fields = ["states", "actions", "adv", "etr", "oldflat", "oldv"]
+        fields = _SAMPLE_FIELDS
         orig = {f: getattr(batch, f) for f in fields}
         for f in fields:
             assert orig[f].is_contiguous(), f"curation needs contiguous {f}"
@@ -1905,7 +1783,7 @@ class DPPOEngine:
                     self.comm.send(send_copy[f], dst)
                 elif r == dst:
                     self.comm.recv(orig[f], s)
-        return _dc.replace(batch, valid=True)
+        return dataclasses.replace(batch, valid=True)
 
     def train_round(self) -> Tuple[Dict[str, float], bool]:
         """One full synchronous round. Returns (rank0-view stats, stop)."""

@@ -125,6 +125,30 @@ def test_relu_and_128_wide_path():
     torch.testing.assert_close(pdflat, flat_ref, atol=3e-5, rtol=3e-5)
 
 
+def test_graphed_update_warmup_failure_steps_the_round_once():
+    """A host exception in the middle of the capture warm-up, after real
+    optimizer steps already ran: the state is restored before the fall-back
+    to the uncaptured path, so the round is stepped once, not twice."""
+    eng = make_engine()
+    eng.sync_oldpi()
+    batch = eng.collect()
+    steps0 = eng.optimizer.step_count
+    real_body, calls = eng._update_body, []
+
+    def body(b):
+        calls.append(1)
+        if len(calls) == 2:
+            raise RuntimeError("injected warm-up failure")
+        real_body(b)
+
+    eng._update_body = body
+    eng._update_graphed(batch, 0.9)
+    del eng._update_body
+    assert len(calls) == 2
+    assert eng._graph_failed
+    assert eng.optimizer.step_count - steps0 == eng.cfg.UPDATE_STEPS
+
+
 def test_graphed_update_matches_ungraphed():
     """The hipGraph-captured update replays to (nearly) the same parameters
     as the uncaptured fused path across rounds with varying l_mul."""
