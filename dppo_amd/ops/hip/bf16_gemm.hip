@@ -856,18 +856,13 @@ void bf16_mm256(torch::Tensor A, torch::Tensor B, torch::Tensor C,
     const char* e = getenv("DPPO_MM256_2BAR");
     return e != nullptr && e[0] == '1';
   }();
-  static const int nph = []() {
-    const char* e = getenv("DPPO_MM256_PH");
-    return e ? atoi(e) : 2;  // 2 phases/tile measured fastest
-  }();
-  static const int mfma = []() {
-    const char* e = getenv("DPPO_MM256_MFMA");
-    // 16x16x32 measured FASTER than 32x32x16 here (1160-1199 vs
-    // 1020-1047 TF/s) despite the larger µbench ceiling — the 32x32
-    // form's 4-deep chained accumulator + 16-reg C/D operands lose more
-    // than the halved instruction count buys.  Kept for ablation.
-    return e ? atoi(e) : 16;
-  }();
+  // 2 phases/tile measured fastest
+  static const int nph = env_int("DPPO_MM256_PH", 2);
+  // 16x16x32 measured FASTER than 32x32x16 here (1160-1199 vs
+  // 1020-1047 TF/s) despite the larger µbench ceiling — the 32x32
+  // form's 4-deep chained accumulator + 16-reg C/D operands lose more
+  // than the halved instruction count buys.  Kept for ablation.
+  static const int mfma = env_int("DPPO_MM256_MFMA", 16);
   const bool want32 = (mfma == 32) && CT.numel() == 0;  // 32-variant has
                                                         // no dual-write
   if (two_bar)
@@ -884,11 +879,8 @@ void bf16_mm256(torch::Tensor A, torch::Tensor B, torch::Tensor C,
       const char* e = getenv("DPPO_MM256_SPRIO");
       return e != nullptr && e[0] == '1';
     }();
-    static const int nimg = []() {
-      const char* e = getenv("DPPO_MM256_IMG");
-      return e ? atoi(e) : 2;  // 3 = third A image (UNVALIDATED on
-                               // hardware this round — ROADMAP #1a)
-    }();
+    // 3 = third A image (UNVALIDATED on hardware this round — ROADMAP #1a)
+    static const int nimg = env_int("DPPO_MM256_IMG", 2);
     if (nimg == 3)
       hipLaunchKernelGGL((bf16_mm256_kernel<2, false, false, 3>),
                          dim3((unsigned)grid), dim3(512), 0, stream, a);

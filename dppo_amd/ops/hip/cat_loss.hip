@@ -8,7 +8,7 @@
 // the shifted-logit entropy (:148-153), the importance ratio with both
 // PPO clips and the three block-reduced means (reference PPO.py:29-40),
 // plus Gumbel-max sampling argmax(logits - log(-log U)) (:154-156) with
-// the same counter-based RNG family as rollout.hip.
+// the rollout's counter-based RNG (rollout_math.h).
 //
 // Layout: wave-per-row for the loss kernels (lane j owns logit column j,
 // K <= 64; coalesced row loads, butterfly wave reductions so every lane
@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "ppo_math.h"
+#include "rollout_math.h"
 
 namespace {
 
@@ -37,24 +38,6 @@ DEV_INLINE float wave_allreduce_max(float x) {
   for (int off = WAVE / 2; off > 0; off >>= 1)
     x = fmaxf(x, __shfl_xor(x, off, WAVE));
   return x;
-}
-
-// counter-based RNG (same lowbias32 family as rollout.hip)
-DEV_INLINE unsigned cat_lowbias32(unsigned x) {
-  x ^= x >> 16;
-  x *= 0x7feb352dU;
-  x ^= x >> 15;
-  x *= 0x846ca68bU;
-  x ^= x >> 16;
-  return x;
-}
-
-// uniform in (0, 1]
-DEV_INLINE float cat_uniform(unsigned seed, unsigned row, unsigned ctr,
-                             unsigned slot) {
-  unsigned h = cat_lowbias32(seed ^ row * 0x9E3779B9U ^ ctr * 0x85EBCA6BU ^
-                             slot * 0xC2B2AE35U);
-  return ((h >> 8) + 1) * (1.0f / 16777217.0f);
 }
 
 // Per-row categorical quantities every lane ends up holding.
@@ -194,7 +177,7 @@ __global__ void cat_sample_kernel(const float* __restrict__ logits,
     int arg = 0;
     for (int j = 0; j < K; ++j) {
       // Gumbel-max: argmax(logits - log(-log U)) (distributions.py:154-156)
-      const float u = cat_uniform(seed, (unsigned)b, ctr, (unsigned)j);
+      const float u = rng_uniform(seed, (int)b, (int)ctr, j);
       const float gv = row[j] - __logf(-__logf(u));
       if (gv > best) {
         best = gv;

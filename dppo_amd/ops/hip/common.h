@@ -8,6 +8,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #define DEV_INLINE __device__ __forceinline__
 
 constexpr int WAVE = 64;  // CDNA wavefront width (not 32)
@@ -46,6 +48,14 @@ DEV_INLINE int64_t gidx() {
 
 DEV_INLINE int64_t gstride() {
   return static_cast<int64_t>(gridDim.x) * blockDim.x;
+}
+
+// Integer tuning knob from the environment (docs/KNOBS.md); `def` when
+// unset.  Call sites that must not re-read per call cache the result in a
+// function-local static.
+inline int env_int(const char* name, int def) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : def;
 }
 
 // Grid sizing for memory-bound elementwise/reduction kernels: cap the

@@ -1,4 +1,5 @@
-// MFMA f32 GEMM kernels for the MLP update path (gfx950).
+// MFMA f32 GEMM kernels for the MLP forward / update path and the v3
+// rollout's fused env step (gfx950).
 //
 // gfx950 has exact fp32-input MFMA (v_mfma_f32_32x32x2_f32: bitwise a
 // k-ordered fmaf chain, 157 TF chip peak = the f32 vector peak — cdna
@@ -17,6 +18,10 @@
 //               policy for one 128-row tile in one launch, on gemm_fwd's
 //               glds K loop and epilogue helpers: bitwise the three
 //               gemm_fwd calls, without reading h1 / h2 / pdflat back.
+//   gemm_env_step: the rollout's G = [XV|a] @ [U;B] GEMM with the env
+//               transition as its epilogue (gemm_fwd_glds_kernel<*, true>)
+//               + env_finish2_kernel; the per-element math is
+//               rollout_math.h's, shared with rollout.hip's split kernels.
 //   dgrad modes (activation 3/4): C = act'(aux) * (X @ Wt) — the
 //               backward chain reuses torch weight layouts directly.
 //   dw_mfma:    dW[out,in] += delta^T @ acts, split-K over row blocks
@@ -32,19 +37,18 @@
 // staging — BK=16 single-buffer with 5-6 blocks/CU is the measured
 // optimum.
 //
-// Fragment layout (cdna guide §3, v_mfma_f32_32x32x2_f32):
-//   lane l: A[i = l&31][k = l>>5], B[k = l>>5][j = l&31]
-//   C/D reg r (of 16): row = (r&3) + 8*(r>>2) + 4*(l>>5), col = l&31.
+// Fragment layout of v_mfma_f32_32x32x2_f32: mfma_frag.h.
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
 #include "common.h"
+#include "mfma_frag.h"
+#include "rollout_math.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int BK = 16;        // K-step per stage
@@ -52,10 +56,6 @@ constexpr int M_WAVE = 32;    // rows per wave tile
 constexpr int FWD_WAVES = 4;  // waves per block (each owns 32 rows)
 constexpr int FWD_M = FWD_WAVES * M_WAVE;  // 128 rows per block
 constexpr int MAX_NT = 4;     // 32-col accumulator tiles per wave
-
-DEV_INLINE int cd_row(int reg, int lane) {
-  return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-}
 
 // ---------------------------------------------------------------------------
 // Forward layer: C = act(X @ Wt + b).  heads_mode splits the epilogue.
@@ -106,28 +106,59 @@ struct FwdArgs {
   int step;
 };
 
-// counter-based RNG — formulas identical to rollout.hip's env path
-DEV_INLINE unsigned g_lowbias32(unsigned x) {
-  x ^= x >> 16;
-  x *= 0x7feb352dU;
-  x ^= x >> 15;
-  x *= 0x846ca68bU;
-  x ^= x >> 16;
+// bias + activation of one accumulator element (layer modes 0 relu,
+// 1 tanh, 2 none)
+DEV_INLINE float fwd_bias_act(float acc, float bv, int activation) {
+  float x = acc + bv;
+  if (activation == 0) x = fmaxf(x, 0.f);
+  else if (activation == 1) x = fast_tanhf(x);
   return x;
 }
-DEV_INLINE float2 g_rng_normal2(unsigned seed, int env, int step, int slot) {
-  const unsigned h = g_lowbias32(seed ^ (unsigned)env * 0x9E3779B9U ^
-                                 (unsigned)step * 0x85EBCA6BU ^
-                                 (unsigned)slot * 0xC2B2AE35U);
-  const float u1 = ((h >> 16) + 1) * (1.0f / 65537.0f);
-  const float u2 = (h & 0xFFFFu) * (1.0f / 65536.0f);
-  const float r = sqrtf(-2.0f * __logf(u1));
-  float sn, cs;
-  __sincosf(6.2831853071795865f * u2, &sn, &cs);
-  return make_float2(r * cs, r * sn);
+
+// one output element by heads mode: 2 = padded heads (N includes pad
+// columns so N%4==0 shapes can take the glds kernel; v at column N-2,
+// columns >= N-1 are the zero-weight pad, discarded), 1 = v at N-1
+DEV_INLINE void fwd_store(float* C, float* v, int heads, int N, int ldc,
+                          int64_t row, int col, float x) {
+  if (heads == 2) {
+    if (col == N - 2) v[row] = x;
+    else if (col < N - 2) C[row * ldc + col] = x;
+  } else if (heads) {
+    if (col == N - 1) v[row] = x;
+    else C[row * ldc + col] = x;
+  } else {
+    C[row * ldc + col] = x;
+  }
 }
-DEV_INLINE float g_rng_normal(unsigned seed, int env, int step, int slot) {
-  return g_rng_normal2(seed, env, step, slot).x;
+
+// Layer epilogue of one wave's [32 rows][NT*32 cols] accumulator tile at
+// (b0 + 32*wave, n0): bias + activation, or act'(aux) * acc in the dgrad
+// modes, then the heads-mode store.  Shared by the plain and glds kernels;
+// the pipe kernel keeps the same code written out (see there).
+template <int NT>
+DEV_INLINE void fwd_epilogue(const FwdArgs& a, const f32x16 (&acc)[NT],
+                             int64_t b0, int n0, int wave, int lane) {
+  #pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int col = n0 + t * M_WAVE + (lane & 31);
+    if (col < a.N) {
+      const float bv = (a.activation >= 3) ? 0.f : a.bias[col];
+      #pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t row = b0 + wave * M_WAVE + cd_row(r, lane);
+        if (row < a.B) {
+          float x;
+          if (a.activation >= 3) {
+            const float h = a.aux[row * a.N + col];
+            x = acc[t][r] * act_grad(h, a.activation == 3);
+          } else {
+            x = fwd_bias_act(acc[t][r], bv, a.activation);
+          }
+          fwd_store(a.C, a.v, a.heads, a.N, a.ldc, row, col, x);
+        }
+      }
+    }
+  }
 }
 
 template <int NT>
@@ -241,42 +272,7 @@ __global__ void gemm_fwd_kernel(FwdArgs a) {
       }
     }
 
-    // ---- epilogue: bias + activation + store ----
-    #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int col = t * M_WAVE + i_l;
-      if (col < a.N && !(a.ablate & 8)) {
-        const float bv = (a.activation >= 3) ? 0.f : a.bias[col];
-        #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int64_t row = b0 + wave * M_WAVE + cd_row(r, lane);
-          if (row < a.B) {
-            float x;
-            if (a.activation >= 3) {
-              const float h = a.aux[row * a.N + col];
-              x = acc[t][r] * ((a.activation == 3) ? (1.f - h * h)
-                                                   : (h > 0.f ? 1.f : 0.f));
-            } else {
-              x = acc[t][r] + bv;
-              if (a.activation == 0) x = fmaxf(x, 0.f);
-              else if (a.activation == 1) x = fast_tanhf(x);
-            }
-            if (a.heads == 2) {
-              // padded heads: N includes pad columns so N%4==0 shapes
-              // can take the glds kernel; v sits at N-2, cols >= N-1
-              // are the zero-weight pad (discarded)
-              if (col == a.N - 2) a.v[row] = x;
-              else if (col < a.N - 2) a.C[row * a.ldc + col] = x;
-            } else if (a.heads) {
-              if (col == a.N - 1) a.v[row] = x;
-              else a.C[row * a.ldc + col] = x;
-            } else {
-              a.C[row * a.ldc + col] = x;
-            }
-          }
-        }
-      }
-    }
+    if (!(a.ablate & 8)) fwd_epilogue<NT>(a, acc, b0, 0, wave, lane);
   }
 }
 
@@ -450,6 +446,8 @@ __global__ void gemm_fwd_pipe_kernel(FwdArgs a) {
       __syncthreads();
     }
 
+    // fwd_epilogue<NT>, kept written out: folded in, <2,16> measured slower
+    // on the L1 shape (profiles/r08_device_dedup.txt)
     #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int col = n0 + t * M_WAVE + i_l;
@@ -470,9 +468,6 @@ __global__ void gemm_fwd_pipe_kernel(FwdArgs a) {
               else if (a.activation == 1) x = fast_tanhf(x);
             }
             if (a.heads == 2) {
-              // padded heads: N includes pad columns so N%4==0 shapes
-              // can take the glds kernel; v sits at N-2, cols >= N-1
-              // are the zero-weight pad (discarded)
               if (col == a.N - 2) a.v[row] = x;
               else if (col < a.N - 2) a.C[row * a.ldc + col] = x;
             } else if (a.heads) {
@@ -642,30 +637,6 @@ DEV_INLINE void glds_fwd_mainloop(const FwdArgs& a, char* smem, int64_t b0,
   __builtin_amdgcn_s_barrier();
 }
 
-// bias + activation of one accumulator element (layer modes 0 relu,
-// 1 tanh, 2 none)
-DEV_INLINE float fwd_bias_act(float acc, float bv, int activation) {
-  float x = acc + bv;
-  if (activation == 0) x = fmaxf(x, 0.f);
-  else if (activation == 1) x = fast_tanhf(x);
-  return x;
-}
-
-// one output element by heads mode: 2 = padded heads (v at column N-2,
-// columns >= N-1 are the zero-weight pad, discarded), 1 = v at N-1
-DEV_INLINE void fwd_store(float* C, float* v, int heads, int N, int ldc,
-                          int64_t row, int col, float x) {
-  if (heads == 2) {
-    if (col == N - 2) v[row] = x;
-    else if (col < N - 2) C[row * ldc + col] = x;
-  } else if (heads) {
-    if (col == N - 1) v[row] = x;
-    else C[row * ldc + col] = x;
-  } else {
-    C[row * ldc + col] = x;
-  }
-}
-
 template <int RING,   // ring depth: 2 (24 KB, 6 blocks/CU — overlap via
                       // MORE co-resident blocks), 3 (36 KB, 4 blocks/CU,
                       // default), 4 (48 KB, 3 blocks/CU — deeper
@@ -784,29 +755,27 @@ __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
               *reinterpret_cast<const float4*>(&a.env_xin[e * a.N + d]);
           float nz[4] = {0.f, 0.f, 0.f, 0.f};
           if (sigma != 0.f) {
-            const float2 p0 = g_rng_normal2(seed, (int)e, step, 1000 + 2 * c);
-            const float2 p1 =
-                g_rng_normal2(seed, (int)e, step, 1000 + 2 * c + 1);
+            const float2 p0 = env_noise_pair(seed, (int)e, step, c, 0);
+            const float2 p1 = env_noise_pair(seed, (int)e, step, c, 1);
             nz[0] = p0.x; nz[1] = p0.y; nz[2] = p1.x; nz[3] = p1.y;
           }
-          v.x = fast_tanhf(xv.x * dv.x + gv.x + sigma * nz[0]);
-          v.y = fast_tanhf(xv.y * dv.y + gv.y + sigma * nz[1]);
-          v.z = fast_tanhf(xv.z * dv.z + gv.z + sigma * nz[2]);
-          v.w = fast_tanhf(xv.w * dv.w + gv.w + sigma * nz[3]);
+          v.x = env_pred(xv.x, dv.x, gv.x, sigma, nz[0]);
+          v.y = env_pred(xv.y, dv.y, gv.y, sigma, nz[1]);
+          v.z = env_pred(xv.z, dv.z, gv.z, sigma, nz[2]);
+          v.w = env_pred(xv.w, dv.w, gv.w, sigma, nz[3]);
           ss = sq4(v);
           const int done = a.tcount[e] + 1 >= a.horizons[e] ? 1 : 0;
           if (done) {
-            v.x = 0.1f * g_rng_normal(seed, (int)e, step, 5000 + d);
-            v.y = 0.1f * g_rng_normal(seed, (int)e, step, 5000 + d + 1);
-            v.z = 0.1f * g_rng_normal(seed, (int)e, step, 5000 + d + 2);
-            v.w = 0.1f * g_rng_normal(seed, (int)e, step, 5000 + d + 3);
+            v.x = env_reset(seed, (int)e, step, d);
+            v.y = env_reset(seed, (int)e, step, d + 1);
+            v.z = env_reset(seed, (int)e, step, d + 2);
+            v.w = env_reset(seed, (int)e, step, d + 3);
           }
           *reinterpret_cast<float4*>(&a.env_x[e * a.N + d]) = v;
         }
         // the 16 lanes of a row hold the whole panel's pred^2: one plain
-        // store per (panel, row) keeps the reward deterministic; chunk
-        // sums, xor tree and env_finish2's ascending panel sum are the
-        // order env_finish_kernel uses too (bitwise-equal rewards)
+        // store per (panel, row) keeps the reward deterministic, in the
+        // shared sum order (rollout_math.h)
         #pragma unroll
         for (int off = 8; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 16);
         if (c4 == 0 && rok) a.env_rsum[(int64_t)blockIdx.y * a.B + e] = ss;
@@ -846,28 +815,7 @@ __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
     return;
   }
 
-  #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int col = n0 + t * M_WAVE + i_l;
-    if (col < a.N) {
-      const float bv = (a.activation >= 3) ? 0.f : a.bias[col];
-      #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = b0 + wave * M_WAVE + cd_row(r, lane);
-        if (row < a.B) {
-          float x;
-          if (a.activation >= 3) {
-            const float h = a.aux[row * a.N + col];
-            x = acc[t][r] * ((a.activation == 3) ? (1.f - h * h)
-                                                 : (h > 0.f ? 1.f : 0.f));
-          } else {
-            x = fwd_bias_act(acc[t][r], bv, a.activation);
-          }
-          fwd_store(a.C, a.v, a.heads, a.N, a.ldc, row, col, x);
-        }
-      }
-    }
-  }
+  fwd_epilogue<NT>(a, acc, b0, n0, wave, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -915,14 +863,6 @@ struct MlpFwdArgs {
   int step, xva_w, va_off;
   float act_low, act_high;
 };
-
-// counter-based uniform in (0, 1] — rollout.hip's rng_uniform
-DEV_INLINE float g_rng_uniform(unsigned seed, int env, int step, int slot) {
-  const unsigned h = g_lowbias32(seed ^ (unsigned)env * 0x9E3779B9U ^
-                                 (unsigned)step * 0x85EBCA6BU ^
-                                 (unsigned)slot * 0xC2B2AE35U);
-  return ((h >> 8) + 1) * (1.0f / 16777217.0f);
-}
 
 // acc = image[32][64] @ W[64][N] in the split call's order: four 16-wide
 // k-stages starting at stage `phase`, k ascending inside a stage.  Columns
@@ -1043,12 +983,8 @@ __global__ void mlp_fwd_fused_kernel(MlpFwdArgs m) {
       if (e < B) {
         const float mean = img[lr * IMG_LD + j];
         const float logstd = img[lr * IMG_LD + A + j];
-        float a_ = mean + __expf(logstd) * g_rng_normal(seed, (int)e, step, j);
-        const float u_dec = g_rng_uniform(seed, (int)e, step, 90001);
-        if (u_dec < eps) {
-          const float u = g_rng_uniform(seed, (int)e, step, 90010 + j);
-          a_ = m.act_low + (m.act_high - m.act_low) * u;
-        }
+        const float a_ = box_sample(mean, logstd, seed, e, step, j, eps,
+                                    m.act_low, m.act_high);
         m.actions[e * A + j] = a_;
         m.xva[e * m.xva_w + m.va_off + j] = a_;
       }
@@ -1068,18 +1004,8 @@ __global__ void env_finish2_kernel(const float* __restrict__ rsum,
   for (int64_t e = gidx(); e < E; e += gstride()) {
     float ss = 0.f;
     for (int p = 0; p < npanels; ++p) ss += rsum[(int64_t)p * E + e];
-    const float r = 1.0f - ss / (float)D;
-    rewards[e] = r;
-    float ep = epr[e] + r;
-    int tc = t[e] + 1;
-    const int done = tc >= horizons[e] ? 1 : 0;
-    dones[e] = (float)done;
-    if (done) {
-      ep = 0.f;
-      tc = 0;
-    }
-    epr[e] = ep;
-    t[e] = tc;
+    int done;
+    episode_step(ss, D, e, done, horizons, t, epr, rewards, dones);
   }
 }
 
@@ -1493,11 +1419,24 @@ __global__ void db_reduce_kernel(const float* __restrict__ db_slab,
 // B=1M); long-K streams keep the 3-deep ring (L1t K=376: wash; ring 4
 // measured slower).  DPPO_FWD_RING=2/3/4 forces a depth.
 static int fwd_ring_for(int K) {
-  static const int ring_env = []() {
-    const char* e = getenv("DPPO_FWD_RING");
-    return e ? atoi(e) : 0;  // 0 = by shape
-  }();
+  static const int ring_env = env_int("DPPO_FWD_RING", 0);  // 0 = by shape
   return ring_env ? ring_env : (K <= 128 ? 2 : 3);
+}
+
+// gemm_fwd_glds_kernel<ring, ENV> for a runtime ring depth (3 unless 2 or 4)
+template <bool ENV>
+static void launch_glds(int ring, dim3 grid, hipStream_t stream,
+                        const FwdArgs& a) {
+  const dim3 block(FWD_WAVES * 64);
+  if (ring == 2)
+    hipLaunchKernelGGL((gemm_fwd_glds_kernel<2, ENV>), grid, block, 0, stream,
+                       a);
+  else if (ring == 4)
+    hipLaunchKernelGGL((gemm_fwd_glds_kernel<4, ENV>), grid, block, 0, stream,
+                       a);
+  else
+    hipLaunchKernelGGL((gemm_fwd_glds_kernel<3, ENV>), grid, block, 0, stream,
+                       a);
 }
 
 void gemm_fwd(torch::Tensor X, torch::Tensor Wt, torch::Tensor bias,
@@ -1553,14 +1492,8 @@ void gemm_fwd(torch::Tensor X, torch::Tensor Wt, torch::Tensor bias,
   // T14 register-pipelined variant (see gemm_fwd_pipe_kernel).  Its
   // branchless clamped loads need K>=4 (X / layout-1 W rows) and, for
   // layout 0, N>=4 (W rows); tiny shapes take the plain kernel.
-  static const int pipe_env = []() {
-    const char* e = getenv("DPPO_GEMM_PIPE");
-    return e ? atoi(e) : 1;
-  }();
-  static const int pbk_env = []() {
-    const char* e = getenv("DPPO_GEMM_PBK");
-    return e ? atoi(e) : 0;  // 0 = per-shape heuristic
-  }();
+  static const int pipe_env = env_int("DPPO_GEMM_PIPE", 1);
+  static const int pbk_env = env_int("DPPO_GEMM_PBK", 0);  // 0 = by shape
   // K%4!=0 is allowed for the dgrad-from-gh call (activation>=3,
   // wt_layout 0): its X is the gh buffer, allocated with a float4 of
   // slack, and the overhang columns multiply zeroed W rows >= K.
@@ -1568,10 +1501,7 @@ void gemm_fwd(torch::Tensor X, torch::Tensor Wt, torch::Tensor bias,
                     (K % 4 == 0 || (wt_layout == 0 && activation >= 3)) &&
                     (wt_layout == 1 || (N >= 4 && N % 4 == 0));
   const int pbk = pbk_env ? pbk_env : 16;
-  static const int glds_env = []() {
-    const char* e = getenv("DPPO_GEMM_GLDS");
-    return e ? atoi(e) : 1;
-  }();
+  static const int glds_env = env_int("DPPO_GEMM_GLDS", 1);
   // glds 3-buffer streaming variant: NT==2 only (wave-uniform vmcnt),
   // layout-0 W, 16-B-aligned rows (K%4==0, N%4==0), no ablation hooks
   const bool glds_ok = glds_env && !a.ablate && wt_layout == 0 &&
@@ -1579,18 +1509,9 @@ void gemm_fwd(torch::Tensor X, torch::Tensor Wt, torch::Tensor bias,
                        a.activation != 9999;
   const int ring_sel = fwd_ring_for(a.K);
   #define DISPATCH_FWD(NTV, NPANEL)                                          \
-    if (glds_ok && NTV == 2 && ring_sel == 2)                                \
-      hipLaunchKernelGGL(gemm_fwd_glds_kernel<2>,                            \
-                         dim3((unsigned)grid_pipe, NPANEL),                  \
-                         dim3(FWD_WAVES * 64), 0, stream, a);                \
-    else if (glds_ok && NTV == 2 && ring_sel == 4)                           \
-      hipLaunchKernelGGL(gemm_fwd_glds_kernel<4>,                            \
-                         dim3((unsigned)grid_pipe, NPANEL),                  \
-                         dim3(FWD_WAVES * 64), 0, stream, a);                \
-    else if (glds_ok && NTV == 2)                                            \
-      hipLaunchKernelGGL(gemm_fwd_glds_kernel<3>,                            \
-                         dim3((unsigned)grid_pipe, NPANEL),                  \
-                         dim3(FWD_WAVES * 64), 0, stream, a);                \
+    if (glds_ok && NTV == 2)                                                 \
+      launch_glds<false>(ring_sel, dim3((unsigned)grid_pipe, NPANEL), stream, \
+                         a);                                                 \
     else if (pipe && pbk == 32)                                              \
       hipLaunchKernelGGL((gemm_fwd_pipe_kernel<NTV, 32>),                    \
                          dim3(grid_pipe, NPANEL), dim3(FWD_WAVES * 64), 0,   \
@@ -1756,19 +1677,7 @@ void gemm_env_step(torch::Tensor xva, torch::Tensor M, torch::Tensor xin,
   hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
   const int64_t tiles = (E + FWD_M - 1) / FWD_M;
   const dim3 grid((unsigned)tiles, (unsigned)panels);
-  switch (fwd_ring_for(K)) {
-    case 2:
-      hipLaunchKernelGGL((gemm_fwd_glds_kernel<2, true>), grid,
-                         dim3(FWD_WAVES * 64), 0, stream, a);
-      break;
-    case 4:
-      hipLaunchKernelGGL((gemm_fwd_glds_kernel<4, true>), grid,
-                         dim3(FWD_WAVES * 64), 0, stream, a);
-      break;
-    default:
-      hipLaunchKernelGGL((gemm_fwd_glds_kernel<3, true>), grid,
-                         dim3(FWD_WAVES * 64), 0, stream, a);
-  }
+  launch_glds<true>(fwd_ring_for(K), grid, stream, a);
   hipLaunchKernelGGL(env_finish2_kernel, dim3(elementwise_grid(E, 256)),
                      dim3(256), 0, stream, rsum.data_ptr<float>(),
                      t.data_ptr<int>(), horizons.data_ptr<int>(),
@@ -1826,112 +1735,85 @@ void dw_mfma(torch::Tensor delta, torch::Tensor acts, torch::Tensor grad_buf,
   a.nt = std::min(mt == 2 ? 2 : MAX_NT, (in_dim + M_WAVE - 1) / M_WAVE);
   const int m_tiles = (out_dim + M_WAVE * mt - 1) / (M_WAVE * mt);
   const int n_tiles = (in_dim + a.nt * M_WAVE - 1) / (a.nt * M_WAVE);
-  // enough waves to hide the streamed-operand latency; slab stores make
-  // extra splits nearly free (the reduce is split-chunk parallel)
-  const int target_blocks = 4096;
-  a.splits = std::max(1, target_blocks / std::max(1, m_tiles * n_tiles));
-  a.splits = static_cast<int>(
-      std::min<int64_t>(a.splits, std::max<int64_t>(1, B / 256)));
-
-  auto& slab = dw_scratch(0, (int64_t)a.splits * out_dim * in_dim,
-                          delta.options());
-  auto& db_slab = dw_scratch(1, (int64_t)a.splits * out_dim,
-                             delta.options());
-  // the old kernels' split grid also overwrites every used element, but
-  // a db tail beyond this call's splits must not leak: zero the region
-  db_slab.narrow(0, 0, (int64_t)a.splits * out_dim).zero_();
-  a.slab = slab.data_ptr<float>();
-  a.db_slab = db_slab.data_ptr<float>();
 
   hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
-  static const int dwglds_env = []() {
-    const char* e = getenv("DPPO_DW_GLDS");
-    return e ? atoi(e) : 1;
-  }();
+  static const int dwglds_env = env_int("DPPO_DW_GLDS", 1);
   // 8-wave LDS-staged variant: whole dW tile per block, delta read once
   // <2,4,3> covers wide-acts tiles (dW1: in=obs); <2,2,1> covers the
   // narrow [<=64][<=64] shapes (dW2, padded heads dW)
   const bool glds_wide = in_dim > 192 && in_dim <= 384;
   const bool glds_narrow = in_dim <= 64 && out_dim <= 64;
-  if (dwglds_env && !a.ablate && out_dim <= 64 &&
-      (glds_wide || glds_narrow) && out_dim % 4 == 0 && in_dim % 4 == 0 &&
-      B >= 4096) {
-    const char* sc_env = getenv("DPPO_DW_SPLITS");  // re-read: sweepable
-    const int64_t split_cap = sc_env ? (int64_t)atoll(sc_env) : (int64_t)1024;
+  const bool glds = dwglds_env && !a.ablate && out_dim <= 64 &&
+                    (glds_wide || glds_narrow) && out_dim % 4 == 0 &&
+                    in_dim % 4 == 0 && B >= 4096;
+  if (glds) {
+    // re-read per call: sweepable
+    const int64_t split_cap = env_int("DPPO_DW_SPLITS", 1024);
     a.splits = static_cast<int>(
         std::min<int64_t>(split_cap, std::max<int64_t>(256, B / 4096)));
     a.splits = static_cast<int>(
         std::min<int64_t>(a.splits, std::max<int64_t>(1, B / DWG_K)));
-    {
-      // no empty trailing split: dw_glds_kernel returns early on one and
-      // leaves its slab rows unwritten for the reduce (B = 4099 with 256
-      // splits of 17 rows left 14 of them stale)
-      const int64_t rows_per = (B + a.splits - 1) / a.splits;
-      a.splits = static_cast<int>((B + rows_per - 1) / rows_per);
-    }
-    auto& slab2 = dw_scratch(0, (int64_t)a.splits * out_dim * in_dim,
+    // no empty trailing split: dw_glds_kernel returns early on one and
+    // leaves its slab rows unwritten for the reduce (B = 4099 with 256
+    // splits of 17 rows left 14 of them stale)
+    const int64_t rows_per = (B + a.splits - 1) / a.splits;
+    a.splits = static_cast<int>((B + rows_per - 1) / rows_per);
+  } else {
+    // enough waves to hide the streamed-operand latency; slab stores make
+    // extra splits nearly free (the reduce is split-chunk parallel)
+    const int target_blocks = 4096;
+    a.splits = std::max(1, target_blocks / std::max(1, m_tiles * n_tiles));
+    a.splits = static_cast<int>(
+        std::min<int64_t>(a.splits, std::max<int64_t>(1, B / 256)));
+  }
+
+  auto& slab = dw_scratch(0, (int64_t)a.splits * out_dim * in_dim,
+                          delta.options());
+  auto& db_slab = dw_scratch(1, (int64_t)a.splits * out_dim,
                              delta.options());
-    auto& db_slab2 = dw_scratch(1, (int64_t)a.splits * out_dim,
-                                delta.options());
-    a.slab = slab2.data_ptr<float>();
-    a.db_slab = db_slab2.data_ptr<float>();
-    if (glds_wide)
-      // single 384-wide tile, 5-deep ring (measured: 2-panel <2,2,3,4>
-      // grids with 2 blocks/CU ran 6% SLOWER — the duplicated delta
-      // stage and shorter MFMA chains cost more than the cross-block
-      // barrier overlap bought; both are ~60% of the f32-MFMA floor)
-      hipLaunchKernelGGL((dw_glds_kernel<2, 4, 3, 5>),
-                         dim3((unsigned)a.splits, 1), dim3(512), 0,
-                         stream, a);
-    else
-      hipLaunchKernelGGL((dw_glds_kernel<2, 2, 1>), dim3((unsigned)a.splits),
-                         dim3(256), 0, stream, a);
-    float* dW = grad_buf.data_ptr<float>() + w_off;
-    float* db = (b_off >= 0) ? grad_buf.data_ptr<float>() + b_off : nullptr;
-    float* dW2 =
-        (split_row >= 0) ? grad_buf.data_ptr<float>() + w_off2 : nullptr;
-    float* db2 = (split_row >= 0 && b_off2 >= 0)
-                     ? grad_buf.data_ptr<float>() + b_off2
-                     : nullptr;
-    const int n_chunks = (a.splits + DW_RED_CHUNK - 1) / DW_RED_CHUNK;
-    const dim3 rgrid(elementwise_grid((int64_t)out_dim * in_dim, 256),
-                     n_chunks);
-    hipLaunchKernelGGL(dw_reduce_kernel, rgrid, dim3(256), 0, stream, a.slab,
-                       a.db_slab, dW, db, dW2, db2, out_dim, in_dim, a.splits,
-                       static_cast<int>(split_row));
-    hipLaunchKernelGGL(db_reduce_kernel, dim3(out_dim), dim3(WAVE), 0,
-                       stream, a.db_slab, db, db2, out_dim, a.splits,
-                       static_cast<int>(split_row));
-    return;
+  // every used element is overwritten by the split grid, but a db tail
+  // beyond this call's splits must not leak: zero the region
+  db_slab.narrow(0, 0, (int64_t)a.splits * out_dim).zero_();
+  a.slab = slab.data_ptr<float>();
+  a.db_slab = db_slab.data_ptr<float>();
+
+  if (glds && glds_wide) {
+    // single 384-wide tile, 5-deep ring (measured: 2-panel <2,2,3,4>
+    // grids with 2 blocks/CU ran 6% SLOWER — the duplicated delta
+    // stage and shorter MFMA chains cost more than the cross-block
+    // barrier overlap bought; both are ~60% of the f32-MFMA floor)
+    hipLaunchKernelGGL((dw_glds_kernel<2, 4, 3, 5>),
+                       dim3((unsigned)a.splits, 1), dim3(512), 0, stream, a);
+  } else if (glds) {
+    hipLaunchKernelGGL((dw_glds_kernel<2, 2, 1>), dim3((unsigned)a.splits),
+                       dim3(256), 0, stream, a);
+  } else {
+    const dim3 grid(m_tiles, n_tiles, a.splits);
+    const int key = a.nt * 10 + mt;
+    switch (key) {
+      case 11: hipLaunchKernelGGL((dw_mfma_kernel<1, 1>), grid, dim3(WAVE), 0, stream, a); break;
+      case 21: hipLaunchKernelGGL((dw_mfma_kernel<2, 1>), grid, dim3(WAVE), 0, stream, a); break;
+      case 31: hipLaunchKernelGGL((dw_mfma_kernel<3, 1>), grid, dim3(WAVE), 0, stream, a); break;
+      case 41: hipLaunchKernelGGL((dw_mfma_kernel<4, 1>), grid, dim3(WAVE), 0, stream, a); break;
+      case 12: hipLaunchKernelGGL((dw_mfma_kernel<1, 2>), grid, dim3(WAVE), 0, stream, a); break;
+      case 22: hipLaunchKernelGGL((dw_mfma_kernel<2, 2>), grid, dim3(WAVE), 0, stream, a); break;
+      case 32: hipLaunchKernelGGL((dw_mfma_kernel<3, 2>), grid, dim3(WAVE), 0, stream, a); break;
+      default: hipLaunchKernelGGL((dw_mfma_kernel<4, 2>), grid, dim3(WAVE), 0, stream, a); break;
+    }
   }
-  const dim3 grid(m_tiles, n_tiles, a.splits);
-  const int key = a.nt * 10 + mt;
-  switch (key) {
-    case 11: hipLaunchKernelGGL((dw_mfma_kernel<1, 1>), grid, dim3(WAVE), 0, stream, a); break;
-    case 21: hipLaunchKernelGGL((dw_mfma_kernel<2, 1>), grid, dim3(WAVE), 0, stream, a); break;
-    case 31: hipLaunchKernelGGL((dw_mfma_kernel<3, 1>), grid, dim3(WAVE), 0, stream, a); break;
-    case 41: hipLaunchKernelGGL((dw_mfma_kernel<4, 1>), grid, dim3(WAVE), 0, stream, a); break;
-    case 12: hipLaunchKernelGGL((dw_mfma_kernel<1, 2>), grid, dim3(WAVE), 0, stream, a); break;
-    case 22: hipLaunchKernelGGL((dw_mfma_kernel<2, 2>), grid, dim3(WAVE), 0, stream, a); break;
-    case 32: hipLaunchKernelGGL((dw_mfma_kernel<3, 2>), grid, dim3(WAVE), 0, stream, a); break;
-    default: hipLaunchKernelGGL((dw_mfma_kernel<4, 2>), grid, dim3(WAVE), 0, stream, a); break;
-  }
+
   float* dW = grad_buf.data_ptr<float>() + w_off;
   float* db = (b_off >= 0) ? grad_buf.data_ptr<float>() + b_off : nullptr;
   float* dW2 = (split_row >= 0) ? grad_buf.data_ptr<float>() + w_off2 : nullptr;
   float* db2 = (split_row >= 0 && b_off2 >= 0)
                    ? grad_buf.data_ptr<float>() + b_off2
                    : nullptr;
-  {
-    const int n_chunks = (a.splits + DW_RED_CHUNK - 1) / DW_RED_CHUNK;
-    const dim3 rgrid(elementwise_grid((int64_t)out_dim * in_dim, 256),
-                     n_chunks);
-    hipLaunchKernelGGL(dw_reduce_kernel, rgrid, dim3(256), 0, stream, a.slab,
-                       a.db_slab, dW, db, dW2, db2, out_dim, in_dim, a.splits,
-                       static_cast<int>(split_row));
-    hipLaunchKernelGGL(db_reduce_kernel, dim3(out_dim), dim3(WAVE), 0,
-                       stream, a.db_slab, db, db2, out_dim, a.splits,
-                       static_cast<int>(split_row));
-  }
+  const int n_chunks = (a.splits + DW_RED_CHUNK - 1) / DW_RED_CHUNK;
+  const dim3 rgrid(elementwise_grid((int64_t)out_dim * in_dim, 256), n_chunks);
+  hipLaunchKernelGGL(dw_reduce_kernel, rgrid, dim3(256), 0, stream, a.slab,
+                     a.db_slab, dW, db, dW2, db2, out_dim, in_dim, a.splits,
+                     static_cast<int>(split_row));
+  hipLaunchKernelGGL(db_reduce_kernel, dim3(out_dim), dim3(WAVE), 0, stream,
+                     a.db_slab, db, db2, out_dim, a.splits,
+                     static_cast<int>(split_row));
 }
-

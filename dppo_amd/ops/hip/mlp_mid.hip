@@ -15,8 +15,8 @@
 //   dW2 += dz2^T . h1       db2 += sum dz2
 //   dz1  = act'(h1) * (dz2 . W2)          -> HBM, for dW1
 //
-// All four products are v_mfma_f32_32x32x2_f32 (fragment layout: header of
-// mfma_gemm.hip).  What makes it cheap is that the MFMA C layout (lane =
+// All four products are v_mfma_f32_32x32x2_f32 (fragment layout:
+// mfma_frag.h).  What makes it cheap is that the MFMA C layout (lane =
 // column, the 16 registers = rows) is also the A/B layout of a product
 // that sums over ROWS: h1 and h2 are loaded from HBM straight into that
 // layout (coalesced 128-B row segments, no LDS) and serve as the B operand
@@ -56,11 +56,10 @@
 #include <c10/hip/HIPStream.h>
 
 #include "common.h"
+#include "mfma_frag.h"
 #include "ppo_math.h"
 
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int MID_WAVES = 4;
 constexpr int MID_ROWS = 32;                     // rows per wave tile
@@ -68,10 +67,6 @@ constexpr int MID_TILE = MID_WAVES * MID_ROWS;   // rows per block tile
 constexpr int MID_GRID = N_CU;                   // one block per CU (below)
 constexpr int MID_SPLITS = MID_GRID * MID_WAVES; // one slab per wave
 constexpr int MID_RED_CHUNK = 32;
-
-DEV_INLINE int cd_row(int reg, int lane) {
-  return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-}
 
 struct MidArgs {
   const float* h1;       // [B][H1]
@@ -104,10 +99,6 @@ struct MidArgs {
 // that is needed is that the compiler keeps them in program order
 DEV_INLINE void wave_lds_sync() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
-DEV_INLINE float act_grad(float h, int act_code) {
-  return act_code == 1 ? (1.f - h * h) : (h > 0.f ? 1.f : 0.f);
 }
 
 // rows*w contiguous floats -> LDS rows of stride `ld` (this wave's lanes)
@@ -366,7 +357,7 @@ __global__ void mlp_mid_kernel(MidArgs a) {
       float s = 0.f;
       #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        dz2[t][r] *= act_grad(h2r[t][r], a.act_code);
+        dz2[t][r] *= act_grad(h2r[t][r], a.act_code == 1);
         s += dz2[t][r];
       }
       db2[t] += s;
@@ -411,7 +402,7 @@ __global__ void mlp_mid_kernel(MidArgs a) {
         #pragma unroll
         for (int t = 0; t < NT1; ++t)
           a.dz1[(rb + row) * H1 + 32 * t + c] =
-              dz1[t][r] * act_grad(h1r[t][r], a.act_code);
+              dz1[t][r] * act_grad(h1r[t][r], a.act_code == 1);
       }
     }
     wave_lds_sync();  // next tile's staging overwrites og / un

@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mfma_frag.h"
 #include "ppo_math.h"
 
 namespace {
@@ -128,10 +129,6 @@ struct ChunkArgs {
   float clip_host, entcoeff, vcoeff, beta1, beta2;
   int fuse_adam;
 };
-
-DEV_INLINE float dact(float h, int activation) {
-  return activation ? (1.f - h * h) : (h > 0.f ? 1.f : 0.f);
-}
 
 // TD/TH/TA/TNH = 0 -> runtime shapes (the generic ladder); nonzero ->
 // EXACT compile-time shapes: the LDS map, every i/H-i%H index map, the
@@ -374,7 +371,7 @@ __global__ void mlp_chunk_kernel(ChunkArgs a) {
       for (; u < P + 1; ++u)
         a0 += lds[m.wht + k * m.wsh + u] * lds[m.gh + s * (P + 1) + u];
       lds[dlast + i] =
-          dact(lds[hlast + i], activation) * ((a0 + a1) + (a2 + a3));
+          act_grad(lds[hlast + i], activation) * ((a0 + a1) + (a2 + a3));
     }
     __syncthreads();
 
@@ -390,7 +387,7 @@ __global__ void mlp_chunk_kernel(ChunkArgs a) {
           a3 += lds[m.w2t + k * m.ws2 + u + 3] * lds[m.dh2 + s * H + u + 3];
         }
         lds[m.dh1 + i] =
-            dact(lds[m.h1 + i], activation) * ((a0 + a1) + (a2 + a3));
+            act_grad(lds[m.h1 + i], activation) * ((a0 + a1) + (a2 + a3));
       }
       __syncthreads();
     }

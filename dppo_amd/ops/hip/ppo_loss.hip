@@ -63,13 +63,6 @@ DEV_INLINE void stage_tile(const float* __restrict__ src,
   }
 }
 
-DEV_INLINE GaussRow gauss_row(const float* __restrict__ pdpi,
-                              const float* __restrict__ pdold,
-                              const float* __restrict__ act,
-                              int64_t b, int A) {
-  return ppo_gauss_row(pdpi, pdold, act, b, A);
-}
-
 __launch_bounds__(256)
 __global__ void ppo_gauss_fwd_kernel(
     const float* __restrict__ pdpi, const float* __restrict__ pdold,
@@ -346,7 +339,7 @@ __global__ void ppo_gauss_bwd_kernel(
     int64_t B, int A, float clip, float entcoeff, float vcoeff) {
   const float g = gtotal[0];
   for (int64_t b = gidx(); b < B; b += gstride()) {
-    const GaussRow r = gauss_row(pdpi, pdold, act, b, A);
+    const GaussRow r = ppo_gauss_row(pdpi, pdold, act, b, A);
     const float ratio = __expf(r.logp_pi - r.logp_old);
     const float ab = adv[b];
     const float surr1 = ratio * ab;
@@ -420,8 +413,8 @@ torch::Tensor ppo_loss_gauss_fwd(torch::Tensor pdpi, torch::Tensor pdold,
   auto losses = torch::empty({4}, pdpi.options());
   hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
   const int block = 256;
-  const char* fte = getenv("DPPO_GH_TILE");  // same knob as the gh kernel
-  const int fwd_tile_env = fte ? atoi(fte) : 1;
+  // same knob as the gh kernel; re-read per call
+  const int fwd_tile_env = env_int("DPPO_GH_TILE", 1);
   const int fwd_lds =
       128 * (2 * (2 * A + 1) + (A | 1) + 4) * (int)sizeof(float);
   if (fwd_tile_env && A <= WAVE && fwd_lds <= 65536) {
@@ -709,8 +702,8 @@ torch::Tensor ppo_loss_gauss_gh(torch::Tensor pdflat, torch::Tensor oldflat,
   hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
   const float* cd =
       (clip_dev.numel() > 0) ? clip_dev.data_ptr<float>() : nullptr;
-  const char* ghe = getenv("DPPO_GH_TILE");  // re-read: testable per call
-  const int gh_tile_env = ghe ? atoi(ghe) : 1;
+  // re-read: testable per call
+  const int gh_tile_env = env_int("DPPO_GH_TILE", 1);
   const int lds_bytes =
       GH_TILE * (2 * A + 1 + (ldgh | 1) + (A | 1) + 4) * (int)sizeof(float);
   if (gh_tile_env && lds_bytes <= 65536) {

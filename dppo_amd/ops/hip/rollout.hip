@@ -28,7 +28,8 @@
 //   - Env phase: lanes split the obs dimension d; low-rank dynamics read
 //     transposed Vt/Ut/Bt so every per-lane stream is contiguous.
 //   - RNG: counter-based 32-bit (lowbias32 hash -> Box-Muller):
-//     stateless, deterministic per launch, cheap (no 64-bit mults).
+//     stateless, deterministic per launch, cheap (no 64-bit mults);
+//     functions and slot scheme in rollout_math.h.
 //   - Kernarg pressure: SEVEN pointers total (policy weights are offsets
 //     into the flat parameter buffer; env matrices are one packed blob;
 //     all outputs are one blob carved by the python side) — the previous
@@ -45,6 +46,7 @@
 #include <c10/hip/HIPStream.h>
 
 #include "common.h"
+#include "rollout_math.h"
 
 namespace {
 
@@ -126,46 +128,6 @@ struct RolloutArgs {
                // 2=heads, 4=sampling, 8=env dynamics, 16=buffer writes,
                // 32=env noise only, 64=low/ain inner products only
 };
-
-// ---- counter-based 32-bit RNG --------------------------------------------
-
-DEV_INLINE unsigned lowbias32(unsigned x) {
-  x ^= x >> 16;
-  x *= 0x7feb352dU;
-  x ^= x >> 15;
-  x *= 0x846ca68bU;
-  x ^= x >> 16;
-  return x;
-}
-
-// uniform in (0, 1]
-DEV_INLINE float rng_uniform(unsigned seed, int env, int step, int slot) {
-  unsigned h = lowbias32(seed ^ (unsigned)env * 0x9E3779B9U ^
-                         (unsigned)step * 0x85EBCA6BU ^
-                         (unsigned)slot * 0xC2B2AE35U);
-  return ((h >> 8) + 1) * (1.0f / 16777217.0f);
-}
-
-// One hash -> two 16-bit uniforms -> one Box-Muller pair.  The rollout
-// draws ~1500 normals per block-step (env noise dominates); the naive
-// 2-hash + log + cos per normal made the whole kernel transcendental-
-// bound.  16-bit resolution truncates the tails at ~4.7 sigma, which is
-// statistically invisible for synthetic-env noise and recorded actions.
-DEV_INLINE float2 rng_normal2(unsigned seed, int env, int step, int slot) {
-  const unsigned h = lowbias32(seed ^ (unsigned)env * 0x9E3779B9U ^
-                               (unsigned)step * 0x85EBCA6BU ^
-                               (unsigned)slot * 0xC2B2AE35U);
-  const float u1 = ((h >> 16) + 1) * (1.0f / 65537.0f);
-  const float u2 = (h & 0xFFFFu) * (1.0f / 65536.0f);
-  const float r = sqrtf(-2.0f * __logf(u1));
-  float sn, cs;
-  __sincosf(6.2831853071795865f * u2, &sn, &cs);
-  return make_float2(r * cs, r * sn);
-}
-
-DEV_INLINE float rng_normal(unsigned seed, int env, int step, int slot) {
-  return rng_normal2(seed, env, step, slot).x;
-}
 
 // monotone float<->uint encoding for atomic max (min via -x); raw 0 is the
 // neutral "below every float" element.
@@ -433,9 +395,9 @@ __global__ void rollout_kernel(RolloutArgs a) {
             }
           }
           // epsilon-greedy overlay (Worker.py:149-152): uniform index
-          const float u_dec = rng_uniform(a.seed, ge, step, 90001);
+          const float u_dec = rng_uniform(a.seed, ge, step, RNG_SLOT_EPS);
           if (u_dec < a.eps_explore) {
-            const float u = rng_uniform(a.seed, ge, step, 90010);
+            const float u = rng_uniform(a.seed, ge, step, RNG_SLOT_EPS_ACT);
             arg = (int)(u * A);
           }
           // clamp: u == 1 gives K; non-finite logits must not index past B
@@ -450,11 +412,12 @@ __global__ void rollout_kernel(RolloutArgs a) {
         const int ge = e0 + e;
         const float mean = lds[PD_OFF + e * PD_S + j];
         const float logstd = lds[PD_OFF + e * PD_S + A + j];
+        // box_sample()'s expression, written out: the call reordered the
+        // hoisted setup code of four exact-shape instantiations
         float act = mean + __expf(logstd) * rng_normal(a.seed, ge, step, j);
-        // epsilon-greedy overlay (Worker.py:149-152)
-        const float u_dec = rng_uniform(a.seed, ge, step, 90001);
+        const float u_dec = rng_uniform(a.seed, ge, step, RNG_SLOT_EPS);
         if (u_dec < a.eps_explore) {
-          const float u = rng_uniform(a.seed, ge, step, 90010 + j);
+          const float u = rng_uniform(a.seed, ge, step, RNG_SLOT_EPS_ACT + j);
           act = a.act_low + (a.act_high - a.act_low) * u;
         }
         lds[ACT_OFF + e * ACT_S + j] = act;
@@ -488,14 +451,14 @@ __global__ void rollout_kernel(RolloutArgs a) {
     if (!(a.ablate & 8))
     for (int d = tid; d < D; d += NWAVES * WAVE) {
       const float dd = env_d[d];
-      // one Box-Muller pair per (even env, d) feeds two envs
       float nz[ET];
       #pragma unroll
       for (int q = 0; q < ET; ++q) nz[q] = 0.f;
       if (!(a.ablate & 32)) {
         #pragma unroll
         for (int q = 0; q < ET / 2; ++q) {
-          const float2 p = rng_normal2(a.seed, e0 + 2 * q, step, 1000 + d);
+          const float2 p =
+              rng_normal2(a.seed, e0 + 2 * q, step, RNG_SLOT_ENV + d);
           nz[2 * q] = p.x;
           nz[2 * q + 1] = p.y;
         }
@@ -596,8 +559,7 @@ __global__ void rollout_kernel(RolloutArgs a) {
     for (int e = 0; e < nE; ++e) {
       if (done_lds[e]) {
         for (int d = tid; d < D; d += NWAVES * WAVE)
-          lds[X_OFF + e * MAX_D_S + d] =
-              0.1f * rng_normal(a.seed, e0 + e, step, 5000 + d);
+          lds[X_OFF + e * MAX_D_S + d] = env_reset(a.seed, e0 + e, step, d);
       }
     }
     __syncthreads();
@@ -694,10 +656,13 @@ __global__ void ep_moments_decode_kernel(float* __restrict__ out) {
 // Per-step rollout path (v3): the T-step loop runs as a hipGraph of
 // pipelined MFMA GEMMs (mfma_gemm.hip does the MLP forward AND the env
 // dynamics' low-rank/action matmuls as [E][36] @ [36][D] panels); the two
-// kernels below supply the non-GEMM pieces.  RNG slots/order are IDENTICAL
-// to rollout_kernel, so both paths sample the same actions/noise/resets
-// for a given seed.  seed/eps live in DEVICE memory so one captured graph
-// replays across rounds (they change per round/rollout).
+// kernels below supply the non-GEMM pieces.  Sampling, env transition and
+// episode step are rollout_math.h's, shared with the fused kernels in
+// mfma_gemm.hip that replace these launches (bitwise-equal results); the
+// action, epsilon and reset slots are rollout_kernel's too, the env-noise
+// slot layout is not (slot scheme in rollout_math.h).  seed/eps live in
+// DEVICE memory so one captured graph replays across rounds (they change
+// per round/rollout).
 // ---------------------------------------------------------------------------
 
 // thread per (env, action-dim): sample + epsilon-greedy; also writes the
@@ -717,12 +682,8 @@ __global__ void sample_kernel(const float* __restrict__ pdflat,  // [E][2A]
     const int j = (int)(i % A);
     const float mean = pdflat[e * P + j];
     const float logstd = pdflat[e * P + A + j];
-    float act = mean + __expf(logstd) * rng_normal(seed, (int)e, step, j);
-    const float u_dec = rng_uniform(seed, (int)e, step, 90001);
-    if (u_dec < eps) {
-      const float u = rng_uniform(seed, (int)e, step, 90010 + j);
-      act = act_low + (act_high - act_low) * u;
-    }
+    const float act = box_sample(mean, logstd, seed, e, step, j, eps,
+                                 act_low, act_high);
     actions[e * A + j] = act;
     xva[e * xva_w + va_off + j] = act;
   }
@@ -752,16 +713,11 @@ __global__ void env_finish_kernel(
   if (wid >= E) return;
   const int64_t e = wid;
   // float4 per lane (the v3 gate guarantees D%4==0): the scalar version
-  // kept only ~4 B/lane in flight and ran 2x its streaming floor.  Noise
-  // slots differ from the fused kernel (one Box-Muller pair feeds d and
-  // d+1 of the SAME env, slot 1000+d/2) — each path is deterministic per
-  // seed on its own; nothing requires the two paths to share trajectories.
+  // kept only ~4 B/lane in flight and ran 2x its streaming floor.
   constexpr int CMAX = (MAX_D / 4 + WAVE - 1) / WAVE;  // float4 chunks/lane
   const int nc4 = D / 4;
-  // Reward sum in the fused env epilogue's order (mfma_gemm.hip), so the
-  // two paths agree bitwise: per float4 chunk sq4(), the 16 chunks of one
-  // 64-column panel by an xor tree (chunk c = lane + 64*it is position
-  // lane%16 of panel lane/16 + 4*it), then the panels in ascending order.
+  // Reward sum in the shared order (rollout_math.h): chunk c = lane + 64*it
+  // is position lane%16 of panel lane/16 + 4*it.
   float4 xn[CMAX];
   float pp[CMAX];
   #pragma unroll
@@ -775,15 +731,15 @@ __global__ void env_finish_kernel(
       const float4 dv = *reinterpret_cast<const float4*>(&envd[d]);
       float nz[4] = {0.f, 0.f, 0.f, 0.f};
       if (sigma != 0.f) {
-        const float2 p0 = rng_normal2(seed, (int)e, step, 1000 + 2 * c);
-        const float2 p1 = rng_normal2(seed, (int)e, step, 1000 + 2 * c + 1);
+        const float2 p0 = env_noise_pair(seed, (int)e, step, c, 0);
+        const float2 p1 = env_noise_pair(seed, (int)e, step, c, 1);
         nz[0] = p0.x; nz[1] = p0.y; nz[2] = p1.x; nz[3] = p1.y;
       }
       float4 v;
-      v.x = fast_tanhf(xv.x * dv.x + gv.x + sigma * nz[0]);
-      v.y = fast_tanhf(xv.y * dv.y + gv.y + sigma * nz[1]);
-      v.z = fast_tanhf(xv.z * dv.z + gv.z + sigma * nz[2]);
-      v.w = fast_tanhf(xv.w * dv.w + gv.w + sigma * nz[3]);
+      v.x = env_pred(xv.x, dv.x, gv.x, sigma, nz[0]);
+      v.y = env_pred(xv.y, dv.y, gv.y, sigma, nz[1]);
+      v.z = env_pred(xv.z, dv.z, gv.z, sigma, nz[2]);
+      v.w = env_pred(xv.w, dv.w, gv.w, sigma, nz[3]);
       xn[it] = v;
       ps = sq4(v);
     }
@@ -802,20 +758,8 @@ __global__ void env_finish_kernel(
     }
   }
   int done;
-  if (lane == 0) {
-    const float r = 1.0f - ss / D;
-    rewards[e] = r;
-    float ep = epr[e] + r;
-    int tc = t[e] + 1;
-    done = (tc >= horizons[e]) ? 1 : 0;
-    dones[e] = (float)done;
-    if (done) {
-      ep = 0.f;
-      tc = 0;
-    }
-    epr[e] = ep;
-    t[e] = tc;
-  }
+  if (lane == 0)
+    episode_step(ss, D, e, done, horizons, t, epr, rewards, dones);
   done = __shfl(done, 0, WAVE);
   #pragma unroll
   for (int it = 0; it < CMAX; ++it) {
@@ -824,10 +768,10 @@ __global__ void env_finish_kernel(
     const int d = 4 * c;
     float4 v = xn[it];
     if (done) {
-      v.x = 0.1f * rng_normal(seed, (int)e, step, 5000 + d);
-      v.y = 0.1f * rng_normal(seed, (int)e, step, 5000 + d + 1);
-      v.z = 0.1f * rng_normal(seed, (int)e, step, 5000 + d + 2);
-      v.w = 0.1f * rng_normal(seed, (int)e, step, 5000 + d + 3);
+      v.x = env_reset(seed, (int)e, step, d);
+      v.y = env_reset(seed, (int)e, step, d + 1);
+      v.z = env_reset(seed, (int)e, step, d + 2);
+      v.w = env_reset(seed, (int)e, step, d + 3);
     }
     *reinterpret_cast<float4*>(&xout[e * D + d]) = v;
   }
@@ -898,12 +842,10 @@ static RolloutArgs rollout_args(
   return a;
 }
 
-// DPPO_ROLLOUT_MW: absent -> -1 (auto); see rollout_run
+// DPPO_ROLLOUT_MW: absent -> -1 (auto, distinct from an explicit 0); see
+// rollout_run
 static int rollout_mw_env() {
-  static const int mw_env = []() {
-    const char* e = getenv("DPPO_ROLLOUT_MW");
-    return e ? atoi(e) : -1;  // -1 = unset, distinct from explicit 0
-  }();
+  static const int mw_env = env_int("DPPO_ROLLOUT_MW", -1);
   return mw_env;
 }
 
