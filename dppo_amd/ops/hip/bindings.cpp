@@ -104,6 +104,13 @@ void gemm_env_step(torch::Tensor xva, torch::Tensor M, torch::Tensor xin,
                    torch::Tensor rsum, torch::Tensor seed_dev, double sigma,
                    int64_t step, torch::Tensor V, torch::Tensor xvp);
 
+void env_step_rows(torch::Tensor xva, torch::Tensor M, torch::Tensor xin,
+                   torch::Tensor xout, torch::Tensor envd,
+                   torch::Tensor horizons, torch::Tensor t,
+                   torch::Tensor epr, torch::Tensor rewards,
+                   torch::Tensor dones, torch::Tensor seed_dev, double sigma,
+                   int64_t step, torch::Tensor V);
+
 void rollout_env_step(torch::Tensor xin, torch::Tensor xout, torch::Tensor G,
                       torch::Tensor envd, torch::Tensor horizons,
                       torch::Tensor t, torch::Tensor epr,
@@ -188,6 +195,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gemm_env_step", &gemm_env_step,
           "fused G-GEMM + env transition epilogue + per-env finish, "
           "optionally folding the next step's x@V (v3 rollout; gfx950)");
+  mod.def("env_step_rows", &env_step_rows,
+          "row-owning env step: G-GEMM + env transition + per-env finish + "
+          "the next step's x@V in one launch, bitwise gemm_env_step + "
+          "gemm_fwd (v3 rollout; gfx950)");
   mod.def("rollout_env_step", &rollout_env_step,
           "per-step synthetic env finish: tanh/reward/done/reset (gfx950)");
   mod.def("rollout_moments", &rollout_moments,

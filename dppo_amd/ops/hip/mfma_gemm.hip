@@ -22,6 +22,11 @@
 //               transition as its epilogue (gemm_fwd_glds_kernel<*, true>)
 //               + env_finish2_kernel; the per-element math is
 //               rollout_math.h's, shared with rollout.hip's split kernels.
+//   env_step_rows: the same env step with one block owning all column
+//               panels of its rows (env_step_rows_kernel): no reward
+//               partials or finish launch, and the next step's x@V comes
+//               out of the same launch in gemm_fwd's k order — bitwise
+//               gemm_env_step + gemm_fwd.
 //   dgrad modes (activation 3/4): C = act'(aux) * (X @ Wt) — the
 //               backward chain reuses torch weight layouts directly.
 //   dw_mfma:    dW[out,in] += delta^T @ acts, split-K over row blocks
@@ -637,6 +642,77 @@ DEV_INLINE void glds_fwd_mainloop(const FwdArgs& a, char* smem, int64_t b0,
   __builtin_amdgcn_s_barrier();
 }
 
+// ---- fused env-step epilogue pieces ---------------------------------------
+// Shared by gemm_fwd_glds_kernel<*, true> (one block per panel) and
+// env_step_rows_kernel (one block per row tile, all panels); the image
+// layout and its bank arithmetic are described in the former.
+constexpr int ENV_HR = 16;  // rows per wave per repack pass
+
+// pass h of a wave's accumulators (registers 8h..8h+7 of both column tiles
+// = rows 16h..16h+15) -> its [16][64] XOR-swizzled LDS image
+DEV_INLINE void env_tile_dump(float* tile, const f32x16 (&acc)[GLDS_NT],
+                              int h, int lane) {
+  // opaque copy of the lane id: without it the 16 dump addresses of
+  // pass 0 are kept live for pass 1 and the allocator spills them
+  // (80-VGPR budget at 6 blocks/CU); recomputing costs one XOR each
+  int ln = lane;
+  asm volatile("" : "+v"(ln));
+  #pragma unroll
+  for (int t = 0; t < GLDS_NT; ++t) {
+    #pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int lr = cd_row(8 * h + q, ln) - ENV_HR * h;
+      const int cc = t * M_WAVE + (ln & 31);
+      tile[lr * GLDS_NW + ((((cc >> 2) ^ lr) << 2) | (cc & 3))] =
+          acc[t][8 * h + q];
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// One float4 (dims d..d+3 of env e, G in *slot) of the env transition:
+// v = the state written to env_x (fresh if the env is done; zeros where
+// !ok), ss = the whole 64-column panel's pred^2 of that row, summed over
+// its 16 lanes in the shared order (rollout_math.h).  PRE_DONE: the caller
+// read the row's done flag once; otherwise it is read here.
+template <bool PRE_DONE>
+DEV_INLINE void env_tile_f4(const FwdArgs& a, const float4* slot, int64_t e,
+                            int d, int c, bool ok, unsigned seed, float sigma,
+                            int step, const float4& dv, int pre_done,
+                            float4& v, float& ss) {
+  v = make_float4(0.f, 0.f, 0.f, 0.f);
+  ss = 0.f;
+  if (ok) {
+    const float4 gv = *slot;
+    const float4 xv =
+        *reinterpret_cast<const float4*>(&a.env_xin[e * a.N + d]);
+    float nz[4] = {0.f, 0.f, 0.f, 0.f};
+    if (sigma != 0.f) {
+      const float2 p0 = env_noise_pair(seed, (int)e, step, c, 0);
+      const float2 p1 = env_noise_pair(seed, (int)e, step, c, 1);
+      nz[0] = p0.x; nz[1] = p0.y; nz[2] = p1.x; nz[3] = p1.y;
+    }
+    v.x = env_pred(xv.x, dv.x, gv.x, sigma, nz[0]);
+    v.y = env_pred(xv.y, dv.y, gv.y, sigma, nz[1]);
+    v.z = env_pred(xv.z, dv.z, gv.z, sigma, nz[2]);
+    v.w = env_pred(xv.w, dv.w, gv.w, sigma, nz[3]);
+    ss = sq4(v);
+    int done;
+    if constexpr (PRE_DONE) done = pre_done;
+    else done = a.tcount[e] + 1 >= a.horizons[e] ? 1 : 0;
+    if (done) {
+      v.x = env_reset(seed, (int)e, step, d);
+      v.y = env_reset(seed, (int)e, step, d + 1);
+      v.z = env_reset(seed, (int)e, step, d + 2);
+      v.w = env_reset(seed, (int)e, step, d + 3);
+    }
+    *reinterpret_cast<float4*>(&a.env_x[e * a.N + d]) = v;
+  }
+  // the 16 lanes of a row hold the whole panel's pred^2
+  #pragma unroll
+  for (int off = 8; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 16);
+}
+
 template <int RING,   // ring depth: 2 (24 KB, 6 blocks/CU — overlap via
                       // MORE co-resident blocks), 3 (36 KB, 4 blocks/CU,
                       // default), 4 (48 KB, 3 blocks/CU — deeper
@@ -691,7 +767,7 @@ __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
     //     (4q + l/16) ^ row): per 16-lane group the 16 (row, slot) pairs
     //     land on 16 distinct slots, again conflict-free.  An unswizzled
     //     image would put all 16 rows of a column on one bank.
-    constexpr int HR = 16;  // rows per wave per pass
+    constexpr int HR = ENV_HR;
     static_assert(RING * SLOT >= FWD_WAVES * HR * NW * 4 + NW * 16 * 4,
                   "env epilogue image + V panel must fit the ring");
     float* tile = reinterpret_cast<float*>(smem) + wave * (HR * NW);
@@ -724,22 +800,7 @@ __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
     if (cok) dv = *reinterpret_cast<const float4*>(&a.envd[d]);
     #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      // opaque copy of the lane id: without it the 16 dump addresses of
-      // pass 0 are kept live for pass 1 and the allocator spills them
-      // (80-VGPR budget at 6 blocks/CU); recomputing costs one XOR each
-      int ln = lane;
-      asm volatile("" : "+v"(ln));
-      #pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int lr = cd_row(8 * h + q, ln) - HR * h;
-          const int cc = t * M_WAVE + (ln & 31);
-          tile[lr * NW + ((((cc >> 2) ^ lr) << 2) | (cc & 3))] =
-              acc[t][8 * h + q];
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      env_tile_dump(tile, acc, h, lane);
       #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int lr = 4 * j + rsub;
@@ -747,37 +808,12 @@ __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
         const bool rok = e < a.B;
         float4* slot =
             reinterpret_cast<float4*>(&tile[lr * NW + ((c4 ^ lr) << 2)]);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        float ss = 0.f;
-        if (rok && cok) {
-          const float4 gv = *slot;
-          const float4 xv =
-              *reinterpret_cast<const float4*>(&a.env_xin[e * a.N + d]);
-          float nz[4] = {0.f, 0.f, 0.f, 0.f};
-          if (sigma != 0.f) {
-            const float2 p0 = env_noise_pair(seed, (int)e, step, c, 0);
-            const float2 p1 = env_noise_pair(seed, (int)e, step, c, 1);
-            nz[0] = p0.x; nz[1] = p0.y; nz[2] = p1.x; nz[3] = p1.y;
-          }
-          v.x = env_pred(xv.x, dv.x, gv.x, sigma, nz[0]);
-          v.y = env_pred(xv.y, dv.y, gv.y, sigma, nz[1]);
-          v.z = env_pred(xv.z, dv.z, gv.z, sigma, nz[2]);
-          v.w = env_pred(xv.w, dv.w, gv.w, sigma, nz[3]);
-          ss = sq4(v);
-          const int done = a.tcount[e] + 1 >= a.horizons[e] ? 1 : 0;
-          if (done) {
-            v.x = env_reset(seed, (int)e, step, d);
-            v.y = env_reset(seed, (int)e, step, d + 1);
-            v.z = env_reset(seed, (int)e, step, d + 2);
-            v.w = env_reset(seed, (int)e, step, d + 3);
-          }
-          *reinterpret_cast<float4*>(&a.env_x[e * a.N + d]) = v;
-        }
-        // the 16 lanes of a row hold the whole panel's pred^2: one plain
-        // store per (panel, row) keeps the reward deterministic, in the
-        // shared sum order (rollout_math.h)
-        #pragma unroll
-        for (int off = 8; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 16);
+        float4 v;
+        float ss;
+        env_tile_f4<false>(a, slot, e, d, c, rok && cok, seed, sigma, step, dv,
+                           0, v, ss);
+        // one plain store per (panel, row) keeps the reward deterministic,
+        // in the shared sum order (rollout_math.h)
         if (c4 == 0 && rok) a.env_rsum[(int64_t)blockIdx.y * a.B + e] = ss;
         // fold operand: the state actually written (reset rows included),
         // zeros in pad columns and rows
@@ -816,6 +852,173 @@ __global__ void gemm_fwd_glds_kernel(FwdArgs a) {
   }
 
   fwd_epilogue<NT>(a, acc, b0, n0, wave, lane);
+}
+
+// ---------------------------------------------------------------------------
+// Row-owning env step: one block per 128-row tile runs ALL column panels of
+// the G = [XV|a] @ [U;B] GEMM in ascending order, each with
+// gemm_fwd_glds_kernel<2, true>'s K loop (same phase: the row-tile index)
+// and env epilogue pieces, so states are bitwise that kernel's.  Owning
+// every panel of its rows, the block needs no cross-block partials:
+//   - reward: instead of storing the per-(panel, row) pred^2 sum to rsum, a
+//     lane of the row keeps a running sum, ss = 0; ss += partial_p, p ascending
+//     — env_finish2_kernel's order — and calls episode_step() for its row
+//     after the last panel.  No rsum buffer, no finish launch.
+//   - next step's x@V: the finished x' float4s go back into the wave's
+//     image and extend ONE accumulator per 16-row pass on the exact-f32
+//     16x16x4 MFMA.  MFMA j of a panel takes panel columns 4j..4j+3 (lane
+//     group g = lane/16 supplies column 4j+g), so global k ascends strictly
+//     through the panel and from panel to panel: bitwise the k-ordered fmaf
+//     chain of gemm_fwd_pipe_kernel<1,16> on the written states.  Exactly
+//     D/4 MFMAs per row — the last panel's j beyond D are skipped, not
+//     zero-padded (a padded fma would turn a -0 accumulator into +0).  No
+//     xvp partials, no reduce launch, and no third pass over the states.
+// The V panel sits in LDS in natural [k][16] layout (the B read of MFMA j
+// is the 64 consecutive floats at row 4j); the A read of the swizzled
+// image, tile[fi*64 + ((j ^ fi) << 2) + g], touches 64 distinct banks (per
+// 16-lane group 16 distinct slots, the groups 4 distinct dwords of a slot).
+// xva[:, 0:16] is stored after the block's last K loop has read its xva
+// rows; rows are block-private.
+//
+// LDS is the 2-deep ring (24 KB; images + V panel inside it, as in the
+// per-panel kernel), registers are bounded for 4 blocks/CU: 2048 flagship
+// row tiles on 256 CUs are then exactly two full waves of blocks.
+// ---------------------------------------------------------------------------
+
+struct EnvRowsArgs {
+  FwdArgs g;       // X = xva, Wt = M, B = E, K, N = D, env_* (no rsum / xvp)
+  float* xva;      // [E][K]: columns 0..15 receive next-state @ V
+  int* t;          // [E] step counters (g.tcount aliases it)
+  float* epr;      // [E]
+  float* rewards;  // [E]
+  float* dones;    // [E]
+};
+
+__launch_bounds__(FWD_WAVES * 64, 4)
+__global__ void env_step_rows_kernel(EnvRowsArgs m) {
+  constexpr int NT = GLDS_NT;
+  constexpr int NW = GLDS_NW;
+  constexpr int HR = ENV_HR;
+  constexpr int RING = 2;
+  static_assert(RING * GLDS_SLOT >= FWD_WAVES * HR * NW * 4 + NW * 16 * 4,
+                "env epilogue image + V panel must fit the ring");
+  __shared__ __attribute__((aligned(16))) char smem[RING * GLDS_SLOT];
+  const FwdArgs& a = m.g;
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wave = tid / WAVE;
+
+  const int64_t b0 = (int64_t)blockIdx.x * FWD_M;
+  if (b0 >= a.B) return;
+
+  float* tile = reinterpret_cast<float*>(smem) + wave * (HR * NW);
+  float* vs = reinterpret_cast<float*>(smem) + FWD_WAVES * HR * NW;
+  const unsigned seed = (unsigned)(*a.seed_dev);
+  const float sigma = a.sigma;
+  const int step = a.step;
+  const int c4 = lane & 15;   // float4 slot inside the 64-col panel; also
+                              // the A row / B column of the x@V fragments
+  const int rsub = lane >> 4;
+  const int64_t w0 = b0 + wave * M_WAVE;
+
+  // done flag of this lane's 8 rows (pass h, row group j: row 16h+4j+rsub),
+  // read once; the owning lane rewrites t after the last panel
+  unsigned donebits = 0;
+  #pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int64_t e = w0 + 4 * i + rsub;
+    if (e < a.B && a.tcount[e] + 1 >= a.horizons[e]) donebits |= 1u << i;
+  }
+
+  // running pred^2 sum of row 4*c4 + rsub of the wave (lanes c4 < 8): after
+  // the xor tree all 16 lanes of a row group hold the panel's sum, so lane
+  // c4 keeps the one of the group's row pass c4/4, group c4%4 — one register
+  // for the wave's 32 rows instead of eight
+  float ssrow = 0.f;
+  f32x4 xa[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+
+  const int npanels = (a.N + NW - 1) / NW;
+  for (int p = 0; p < npanels; ++p) {
+    const int n0 = p * NW;
+    f32x16 acc[NT];
+    // opaque per panel: keeps the K loop's row pointers from being hoisted
+    // and held (spilled) across the epilogue
+    int64_t b0p = b0;
+    asm volatile("" : "+s"(b0p));
+    glds_fwd_mainloop<RING>(a, smem, b0p, n0, acc);
+
+    // this panel's rows of V ([64][16]; rows >= D zero, never multiplied)
+    // -> LDS, one float4 per thread
+    {
+      const int kl = tid >> 2;
+      const int kr = n0 + kl;
+      float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (kr < a.N)
+        vv = *reinterpret_cast<const float4*>(
+            &a.env_V[(int64_t)kr * 16 + 4 * (tid & 3)]);
+      *reinterpret_cast<float4*>(&vs[kl * 16 + 4 * (tid & 3)]) = vv;
+    }
+    __syncthreads();
+
+    const int d = n0 + 4 * c4;  // first of this lane's 4 dims
+    const int c = d >> 2;       // env_finish_kernel's float4 chunk index
+    const bool cok = d < a.N;   // N%4==0: a float4 is all in or all out
+    float4 dv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (cok) dv = *reinterpret_cast<const float4*>(&a.envd[d]);
+    const int nj = min(16, (a.N - n0) >> 2);  // 4-column groups in the panel
+    // opaque per panel: otherwise the 8 rows' addresses, bounds masks and
+    // RNG hash prefixes are hoisted out of the panel loop and spill
+    int rs = rsub;
+    asm volatile("" : "+v"(rs));
+    #pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      env_tile_dump(tile, acc, h, lane);
+      #pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int lr = 4 * j + rs;
+        const int64_t e = w0 + HR * h + lr;
+        float4* slot =
+            reinterpret_cast<float4*>(&tile[lr * NW + ((c4 ^ lr) << 2)]);
+        float4 v;
+        float ss;
+        env_tile_f4<true>(a, slot, e, d, c, e < a.B && cok, seed, sigma, step,
+                          dv, (int)((donebits >> (4 * h + j)) & 1u), v, ss);
+        if (c4 == 4 * h + j) ssrow += ss;
+        // x@V operand: the state actually written (reset rows included),
+        // zeros in pad rows
+        *slot = v;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      #pragma unroll 4
+      for (int j = 0; j < nj; ++j) {
+        const float av = tile[c4 * NW + ((j ^ c4) << 2) + rsub];
+        const float bv = vs[(4 * j + rsub) * 16 + c4];
+        xa[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, xa[h], 0, 0, 0);
+      }
+    }
+    // images and V panel are read; the next panel's K loop reuses the ring
+    __syncthreads();
+  }
+
+  // per-env bookkeeping by the lane that owns the row's reward sum
+  {
+    const int64_t e = w0 + 4 * c4 + rsub;
+    if (c4 < 8 && e < a.B) {
+      int done;
+      episode_step(ssrow, a.N, e, done, a.horizons, m.t, m.epr, m.rewards,
+                   m.dones);
+    }
+  }
+  // D reg r of pass h: row 16h + 4*(l/16) + r, col l%16; + 0.f is the
+  // zero-bias add of the gemm_fwd call this replaces
+  #pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t e = w0 + HR * h + 4 * rsub + r;
+      if (e < a.B) m.xva[e * a.K + c4] = xa[h][r] + 0.f;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1688,6 +1891,65 @@ void gemm_env_step(torch::Tensor xva, torch::Tensor M, torch::Tensor xin,
                        dim3(elementwise_grid(E * 4, 256)), dim3(256), 0,
                        stream, xvp.data_ptr<float>(), xva.data_ptr<float>(),
                        E, K, panels);
+}
+
+void env_step_rows(torch::Tensor xva, torch::Tensor M, torch::Tensor xin,
+                   torch::Tensor xout, torch::Tensor envd,
+                   torch::Tensor horizons, torch::Tensor t,
+                   torch::Tensor epr, torch::Tensor rewards,
+                   torch::Tensor dones, torch::Tensor seed_dev, double sigma,
+                   int64_t step, torch::Tensor V) {
+  // gemm_env_step + the next step's x@V gemm_fwd in one launch, bitwise
+  // equal to that pair (env_step_rows_kernel)
+  const int64_t E = xva.size(0);
+  const int K = static_cast<int>(xva.size(1));
+  const int D = static_cast<int>(M.size(1));
+  for (const auto& x : {xva, M, xin, xout, envd, epr, rewards, dones, V})
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
+                x.scalar_type() == torch::kFloat);
+  TORCH_CHECK(E >= 1 && xva.dim() == 2 && M.dim() == 2 && xin.dim() == 2);
+  TORCH_CHECK(M.size(0) == K && xin.size(0) == E && xin.size(1) == D);
+  TORCH_CHECK(xout.numel() == E * D && envd.numel() == D);
+  TORCH_CHECK(K % 4 == 0 && K >= 16 && D % 4 == 0 && D >= 4,
+              "env_step_rows needs 16B rows and a 16-column x@V block");
+  TORCH_CHECK(V.dim() == 2 && V.size(0) == D && V.size(1) == 16,
+              "env_step_rows needs V = [D][16]");
+  TORCH_CHECK(horizons.is_cuda() && t.is_cuda() && horizons.is_contiguous() &&
+              t.is_contiguous() && horizons.dtype() == torch::kInt32 &&
+              t.dtype() == torch::kInt32);
+  TORCH_CHECK(horizons.numel() == E && t.numel() == E && epr.numel() == E &&
+              rewards.numel() == E && dones.numel() == E);
+  TORCH_CHECK(seed_dev.is_cuda() && seed_dev.scalar_type() == torch::kLong &&
+              seed_dev.numel() == 1);
+  // (int)e feeds the RNG hash, as in gemm_env_step
+  EnvRowsArgs m{};
+  FwdArgs& a = m.g;
+  a.X = xva.data_ptr<float>();
+  a.Wt = M.data_ptr<float>();
+  a.B = E;
+  a.K = K;
+  a.N = D;
+  a.activation = 5;
+  a.ldc = D;
+  a.env_xin = xin.data_ptr<float>();
+  a.env_x = xout.data_ptr<float>();
+  a.envd = envd.data_ptr<float>();
+  a.horizons = horizons.data_ptr<int>();
+  a.tcount = t.data_ptr<int>();
+  a.seed_dev = reinterpret_cast<const long long*>(seed_dev.data_ptr<int64_t>());
+  a.env_V = V.data_ptr<float>();
+  a.sigma = (float)sigma;
+  a.step = (int)step;
+  m.xva = xva.data_ptr<float>();
+  m.t = t.data_ptr<int>();
+  m.epr = epr.data_ptr<float>();
+  m.rewards = rewards.data_ptr<float>();
+  m.dones = dones.data_ptr<float>();
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  const int64_t tiles = (E + FWD_M - 1) / FWD_M;
+  TORCH_CHECK(tiles <= (1 << 22));
+  hipLaunchKernelGGL(env_step_rows_kernel, dim3((unsigned)tiles),
+                     dim3(FWD_WAVES * 64), 0, stream, m);
 }
 
 // Grow-only scratch cache for the dW split slabs.  Allocating them per

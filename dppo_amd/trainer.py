@@ -126,6 +126,7 @@ class DPPOEngine:
         self._wide_rollout_h_valid = False
         self._fwd_fused_cache = self._mid_mode_cache = None
         self.fwd_fused_launches = {}    # mlp_fwd_fused launches per use
+        self.env_rows_launches = 0      # env_step_rows launches
         self._clip_dev = None           # device clip for captured updates
         self._upd_graph = self._upd_graph_skip = None
         self._graph_failed = False
@@ -698,6 +699,24 @@ class DPPOEngine:
         opt-in."""
         return os.environ.get("DPPO_XV_FOLD", "0") == "1"
 
+    # the DPPO_ENV_ROWS default: what profiles/r09_env_rows.txt measured
+    ENV_ROWS_DEFAULT = "1"
+
+    def _env_rows(self) -> bool:
+        """DPPO_ENV_ROWS=0|1: '1' runs the env step as one env_step_rows
+        launch per step (one block owns all column panels of its rows: no
+        rsum / env_finish2, and the next step's x@V comes out of the same
+        launch in gemm_fwd's k order) where the fused env path is on, the
+        fold is not selected, the env rank is 16 and D % 4 == 0; '0' keeps
+        gemm_env_step + the per-step x@V gemm_fwd.  Both give bitwise-equal
+        results.  Anything else is an error, not a fall-back."""
+        mode = os.environ.get("DPPO_ENV_ROWS", self.ENV_ROWS_DEFAULT)
+        if mode not in ("0", "1"):
+            raise ValueError(f"DPPO_ENV_ROWS={mode!r}: expected '0' or '1'")
+        return (mode == "1" and self._env_fused() and not self._xv_fold()
+                and self.env.rank_eff == 16
+                and self.obs_space.shape[0] % 4 == 0)
+
     # the DPPO_FWD_FUSED default: what profiles/r06_fwd_fused.txt measured
     FWD_FUSED_DEFAULT = "1"
 
@@ -778,6 +797,7 @@ class DPPOEngine:
         # rollout step st writes rows [st*E, (st+1)*E) of each layer
         acts_views = self._acts_views(v3["acts"], T * E)
         fused = self._env_fused()
+        rows = self._env_rows()
         fold = fused and self._xv_fold() and v3["xvp"] is not None
         no_fold = (v3["empty"], v3["empty"])
         # one launch for L1 + L2 + heads + sampling (bitwise equal to the
@@ -808,8 +828,9 @@ class DPPOEngine:
                     ext.gemm_fwd(h, wh, bh, 2, 1, pdflats[st], values[st],
                                  pdflats[st], 1, 0, 0)
             # XV = x @ V into the concat buffer's first rank columns; with
-            # the fold, step st-1's env epilogue already left it there
-            if not fold or st == 0:
+            # env_step_rows or the fold, step st-1's env step already left
+            # it there
+            if not (fold or rows) or st == 0:
                 ext.gemm_fwd(xin, v3["V"], v3["bz_r"], 2, 0, v3["xva"],
                              v3["xva"], v3["xva"], 0, 0, v3["kw"])
             if not fwd_fused:
@@ -822,7 +843,15 @@ class DPPOEngine:
             # the next round's states[0]: one [E][D] stream per step, no
             # mirror write
             xout = states[st + 1] if st + 1 < T else env.x
-            if fused:
+            if rows:
+                # the fused env step below and step st+1's x@V in one launch
+                # (bitwise equal to that pair; see env_step_rows_kernel)
+                ext.env_step_rows(v3["xva"], v3["M"], xin, xout, env.d,
+                                  env.horizons_i32, env.t, self.epr,
+                                  rewards[st], dones[st], v3["seed_dev"],
+                                  float(env.NOISE), st, v3["V"])
+                self.env_rows_launches += 1
+            elif fused:
                 # G = [XV|act] @ [U;B] with the env transition fused into
                 # the GEMM epilogue: the accumulators are repacked through
                 # LDS into env_finish's float4 layout (same math, RNG slots
