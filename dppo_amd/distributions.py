@@ -16,8 +16,8 @@ the same math —
   MultiDiscrete -> MultiCategorical, MultiBinary -> Bernoulli (:231-243).
 
 Everything here runs on CPU or GPU tensors; the HIP fused kernels in
-dppo_amd.ops reproduce the DiagGaussian/Categorical logp+entropy math on
-the training hot path and are tested against this module.
+dppo_amd.ops reproduce each family's logp+entropy math on the training
+hot path and are tested against this module.
 """
 
 from __future__ import annotations
@@ -156,10 +156,11 @@ class MultiCategoricalPd(Pd):
     """Independent categoricals (reference distributions.py:161-182)."""
 
     def __init__(self, nvec, flat: torch.Tensor):
+        self.nvec = tuple(int(n) for n in nvec)  # component sizes
         self.flat = flat
         self.categoricals = [
             CategoricalPd(part)
-            for part in torch.split(flat, list(nvec), dim=-1)
+            for part in torch.split(flat, list(self.nvec), dim=-1)
         ]
 
     def flatparam(self):

@@ -160,7 +160,73 @@ std::vector<torch::Tensor> rollout_run_cat(
     int64_t T, int64_t n_actions, int64_t seed, torch::Tensor out_buf,
     int64_t ablate);
 
+std::vector<torch::Tensor> rollout_run_mcat(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation,
+    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
+    double noise, double eps_explore,
+    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
+    int64_t T, std::vector<int64_t> nvec, int64_t seed, torch::Tensor out_buf,
+    int64_t ablate);
+
+std::vector<torch::Tensor> rollout_run_bern(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation,
+    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
+    double noise, double eps_explore,
+    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
+    int64_t T, int64_t n, int64_t seed, torch::Tensor out_buf,
+    int64_t ablate);
+
+torch::Tensor ppo_loss_mcat_fwd(torch::Tensor lpi, torch::Tensor lold,
+                                torch::Tensor vpred, torch::Tensor oldv,
+                                torch::Tensor act, torch::Tensor adv,
+                                torch::Tensor etr, std::vector<int64_t> nvec,
+                                double clip, double entcoeff, double vcoeff);
+
+std::vector<torch::Tensor> ppo_loss_mcat_bwd(
+    torch::Tensor lpi, torch::Tensor lold, torch::Tensor vpred,
+    torch::Tensor oldv, torch::Tensor act, torch::Tensor adv,
+    torch::Tensor etr, std::vector<int64_t> nvec, double clip,
+    double entcoeff, double vcoeff, torch::Tensor gtotal);
+
+torch::Tensor ppo_loss_bern_fwd(torch::Tensor lpi, torch::Tensor lold,
+                                torch::Tensor vpred, torch::Tensor oldv,
+                                torch::Tensor act, torch::Tensor adv,
+                                torch::Tensor etr, double clip,
+                                double entcoeff, double vcoeff);
+
+std::vector<torch::Tensor> ppo_loss_bern_bwd(
+    torch::Tensor lpi, torch::Tensor lold, torch::Tensor vpred,
+    torch::Tensor oldv, torch::Tensor act, torch::Tensor adv,
+    torch::Tensor etr, double clip, double entcoeff, double vcoeff,
+    torch::Tensor gtotal);
+
+torch::Tensor mcat_sample(torch::Tensor logits, std::vector<int64_t> nvec,
+                          int64_t seed, int64_t ctr);
+
+torch::Tensor bern_sample(torch::Tensor logits, int64_t seed, int64_t ctr);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("rollout_run_mcat", &rollout_run_mcat,
+          "fused T-step rollout, MultiDiscrete/MultiCategorical policy: MLP "
+          "fwd + per-component Gumbel-max + synthetic env, int64 actions "
+          "(gfx950)");
+  mod.def("rollout_run_bern", &rollout_run_bern,
+          "fused T-step rollout, MultiBinary/Bernoulli policy: MLP fwd + "
+          "Bernoulli sample + synthetic env, float 0/1 actions (gfx950)");
+  mod.def("ppo_loss_mcat_fwd", &ppo_loss_mcat_fwd,
+          "fused MultiCategorical PPO loss forward (gfx950)");
+  mod.def("ppo_loss_mcat_bwd", &ppo_loss_mcat_bwd,
+          "fused MultiCategorical PPO loss backward (gfx950)");
+  mod.def("ppo_loss_bern_fwd", &ppo_loss_bern_fwd,
+          "fused Bernoulli PPO loss forward (gfx950)");
+  mod.def("ppo_loss_bern_bwd", &ppo_loss_bern_bwd,
+          "fused Bernoulli PPO loss backward (gfx950)");
+  mod.def("mcat_sample", &mcat_sample,
+          "per-component Gumbel-max sampling, counter-based RNG (gfx950)");
+  mod.def("bern_sample", &bern_sample,
+          "Bernoulli sampling, counter-based RNG (gfx950)");
   mod.def("gae_scan", &gae_scan,
           "segmented GAE reverse scan + whitening (gfx950)");
   mod.def("ppo_loss_gauss_fwd", &ppo_loss_gauss_fwd,

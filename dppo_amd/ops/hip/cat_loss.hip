@@ -20,25 +20,11 @@
 #include <c10/hip/HIPStream.h>
 
 #include "common.h"
+#include "loss_rows.h"
 #include "ppo_math.h"
 #include "rollout_math.h"
 
 namespace {
-
-constexpr float NEG_INF = -3.0e38f;
-
-DEV_INLINE float wave_allreduce_sum(float x) {
-  #pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, WAVE);
-  return x;
-}
-
-DEV_INLINE float wave_allreduce_max(float x) {
-  #pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1)
-    x = fmaxf(x, __shfl_xor(x, off, WAVE));
-  return x;
-}
 
 // Per-row categorical quantities every lane ends up holding.
 struct CatRow {
@@ -113,20 +99,6 @@ __global__ void ppo_cat_fwd_kernel(
     atomicAdd(&acc[1], static_cast<double>(ent));
     atomicAdd(&acc[2], static_cast<double>(val));
   }
-}
-
-__global__ void ppo_cat_finalize_kernel(const double* __restrict__ acc,
-                                        float* __restrict__ losses,  // [4]
-                                        int64_t B, float entcoeff,
-                                        float vcoeff) {
-  const double ib = 1.0 / static_cast<double>(B);
-  const float pol = static_cast<float>(-acc[0] * ib);
-  const float ent = static_cast<float>(-entcoeff * acc[1] * ib);
-  const float val = static_cast<float>(vcoeff * acc[2] * ib);
-  losses[0] = pol;
-  losses[1] = ent;
-  losses[2] = val;
-  losses[3] = pol + ent + val;
 }
 
 __launch_bounds__(256)
@@ -213,7 +185,7 @@ torch::Tensor ppo_loss_cat_fwd(torch::Tensor lpi, torch::Tensor lold,
                      act.data_ptr<int64_t>(), adv.data_ptr<float>(),
                      etr.data_ptr<float>(), acc.data_ptr<double>(), B, K,
                      (float)clip);
-  hipLaunchKernelGGL(ppo_cat_finalize_kernel, dim3(1), dim3(1), 0, stream,
+  hipLaunchKernelGGL(ppo_rows_finalize_kernel, dim3(1), dim3(1), 0, stream,
                      acc.data_ptr<double>(), losses.data_ptr<float>(), B,
                      (float)entcoeff, (float)vcoeff);
   return losses;

@@ -38,12 +38,16 @@
 // Limits (checked in the binding): obs_dim <= 512, hidden <= 128,
 // <= 3 hidden layers, rank <= 32; Box/DiagGaussian with act_dim <= 32, or
 // (FAM_CAT instantiations, rollout_run_cat) Discrete/Categorical with
-// 2 <= n_actions <= 64.  The wide config (BASELINE #5) takes the GEMM path
-// instead.
+// 2 <= n_actions <= 64, or (FAM_MCAT, rollout_run_mcat) MultiDiscrete/
+// MultiCategorical with every n_c >= 2 and sum(n_c) <= 64, or (FAM_BERN,
+// rollout_run_bern) MultiBinary/Bernoulli with n <= 32.  The wide config
+// (BASELINE #5) takes the GEMM path instead.
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
+
+#include <type_traits>
 
 #include "common.h"
 #include "rollout_math.h"
@@ -64,6 +68,9 @@ constexpr int NWAVES = 4;  // waves per block
 // action input and the action output differ.
 constexpr int FAM_BOX = 0;  // DiagGaussian: P = 2A pd params, float actions
 constexpr int FAM_CAT = 1;  // Categorical: P = K logits, int64 action index
+constexpr int FAM_MCAT = 2;  // MultiCategorical: C components, P = sum(n_c)
+                             // logits, int64 actions [C]
+constexpr int FAM_BERN = 3;  // Bernoulli: P = n logits, float 0/1 actions [n]
 constexpr int MAX_K = 64;
 
 // The LDS image is dynamically sized to the ACTUAL dims (obs, widest
@@ -79,6 +86,7 @@ struct LdsMap {
 // P: pd-param width, actw: action slab width, partw: widest row the k-split
 // partial slab holds.  Box: (2A, A, Hmax).  Categorical: (K, 1,
 // max(Hmax, K+1)) — its K+1 head columns may exceed the trunk width.
+// MultiCategorical: (P, C, max(Hmax, P+1)); Bernoulli: (n, n, max(Hmax, n+1)).
 DEV_INLINE LdsMap lds_map(int D, int Hmax, int P, int actw, int partw,
                           int rank, int et) {
   auto r4 = [](int v) { return (v + 3) & ~3; };
@@ -120,7 +128,8 @@ struct RolloutArgs {
   int off_W[MAX_HIDDEN], off_b[MAX_HIDDEN];
   int dims[MAX_HIDDEN + 1];
   int off_Wv, off_bv, off_Wp, off_bp;
-  int n_hidden, act_dim, activation, rank, h_max;  // FAM_CAT: act_dim = K
+  int n_hidden, act_dim, activation, rank, h_max;  // FAM_CAT: act_dim = K,
+                                                   // FAM_MCAT: C, FAM_BERN: n
   float noise, act_low, act_high, eps_explore;
   int T, E, D;
   unsigned seed;
@@ -128,6 +137,26 @@ struct RolloutArgs {
                // 2=heads, 4=sampling, 8=env dynamics, 16=buffer writes,
                // 32=env noise only, 64=low/ain inner products only
 };
+
+// FAM_MCAT adds the component offsets.  A type of its own: the kernarg
+// layout of every other instantiation stays exactly RolloutArgs (their
+// register allocation moved when the shared struct grew).
+struct RolloutArgsMcat : RolloutArgs {
+  int moff[MAX_A + 1];  // first logit column of component c, moff[C] = P
+};
+
+template <int FAM>
+using RolloutArgsOf =
+    std::conditional_t<FAM == FAM_MCAT, RolloutArgsMcat, RolloutArgs>;
+
+// pd-param width P of a family with action width A
+template <int FAM>
+DEV_INLINE int pd_width(const RolloutArgsOf<FAM>& a, int A) {
+  if constexpr (FAM == FAM_MCAT)
+    return a.moff[A];
+  else
+    return (FAM == FAM_BOX) ? 2 * A : A;
+}
 
 // monotone float<->uint encoding for atomic max (min via -x); raw 0 is the
 // neutral "below every float" element.
@@ -157,7 +186,7 @@ template <int MINWAVES, int ET = ENV_TILE, int TD = 0, int TH = 0,
           int TA = 0, int TNH = 0, int TRANK = 0, int TACT = 0,
           int FAM = FAM_BOX>
 __launch_bounds__(NWAVES * 64, MINWAVES)
-__global__ void rollout_kernel(RolloutArgs a) {
+__global__ void rollout_kernel(RolloutArgsOf<FAM> a) {
   const int tid = threadIdx.x;      // block = 4 waves of 64
   const int lane = tid & (WAVE - 1);
   const int wv = tid / WAVE;        // k-split wave index
@@ -167,7 +196,7 @@ __global__ void rollout_kernel(RolloutArgs a) {
   const int nE = TD ? ET : min(ET, a.E - e0);
   const int D = TD ? TD : a.D;
   const int A = TA ? TA : a.act_dim;
-  const int P = (FAM == FAM_CAT) ? A : 2 * A;
+  const int P = pd_width<FAM>(a, A);
   const int T = a.T, E = a.E;
   const int RNK = TRANK ? TRANK : a.rank;
   const int NHID = TNH ? TNH : a.n_hidden;
@@ -177,7 +206,9 @@ __global__ void rollout_kernel(RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const LdsMap lm = (FAM == FAM_CAT)
                         ? lds_map(D, HMAX, P, 1, max(HMAX, P + 1), RNK, ET)
-                        : lds_map(D, HMAX, P, A, HMAX, RNK, ET);
+                    : (FAM == FAM_BOX)
+                        ? lds_map(D, HMAX, P, A, HMAX, RNK, ET)
+                        : lds_map(D, HMAX, P, A, max(HMAX, P + 1), RNK, ET);
   const int X_OFF = lm.x, H0_OFF = lm.h0, H1_OFF = lm.h1, PD_OFF = lm.pd;
   const int ACT_OFF = lm.act, XV_OFF = lm.xv, PART_OFF = lm.part;
   const int MAX_D_S = lm.xs, MAX_H_S = lm.hs;
@@ -185,8 +216,8 @@ __global__ void rollout_kernel(RolloutArgs a) {
             ACT_S = (FAM == FAM_CAT) ? 4 : (A + 3) & ~3,
             XV_S = (RNK + 3) & ~3;
   // k-split partial row stride: the trunk width for Box (unchanged map);
-  // Categorical widens it to hold the K+1 head columns
-  const int PART_S = (FAM == FAM_CAT) ? lm.ps : MAX_H_S;
+  // the logit families widen it to hold the P+1 head columns
+  const int PART_S = (FAM == FAM_BOX) ? MAX_H_S : lm.ps;
   float* val_lds = &lds[lm.val];
   float* rsum_lds = &lds[lm.rsum];
   float* epr_lds = &lds[lm.epr];
@@ -199,14 +230,18 @@ __global__ void rollout_kernel(RolloutArgs a) {
   const float* env_Vt = env_d + D;
   const float* env_U = env_Vt + (int64_t)RNK * D;
   const float* env_B = env_U + (int64_t)RNK * D;
-  // output blob offsets (Categorical: the int64 action indices lead the
-  // blob so they are 8-byte aligned; no float action region)
+  // output blob offsets (Categorical, MultiCategorical: the int64 action
+  // indices lead the blob so they are 8-byte aligned; no float action
+  // region.  Bernoulli: Box's layout with P = n)
+  constexpr bool INT_ACT = (FAM == FAM_CAT || FAM == FAM_MCAT);
   float* out_states =
-      a.out + ((FAM == FAM_CAT) ? 2 * (int64_t)T * E : (int64_t)0);
+      a.out + ((FAM == FAM_CAT)    ? 2 * (int64_t)T * E
+               : (FAM == FAM_MCAT) ? 2 * (int64_t)T * E * A
+                                   : (int64_t)0);
   float* out_pdflats = out_states + (int64_t)T * E * D;
   float* out_actions = out_pdflats + (int64_t)T * E * P;
   float* out_values =
-      out_actions + ((FAM == FAM_CAT) ? (int64_t)0 : (int64_t)T * E * A);
+      out_actions + (INT_ACT ? (int64_t)0 : (int64_t)T * E * A);
   float* out_rewards = out_values + (int64_t)T * E;
   float* out_dones = out_rewards + (int64_t)T * E;
   float* out_boot = out_dones + (int64_t)T * E;
@@ -225,6 +260,11 @@ __global__ void rollout_kernel(RolloutArgs a) {
     // action indices address env B rows: keep every tile slot (tail envs,
     // ablated sampling) a valid row
     if (tid < ET) lds[ACT_OFF + tid * ACT_S] = __int_as_float(0);
+  }
+  if constexpr (FAM == FAM_MCAT) {
+    // as above, for every (tile slot, component): class 0 is a valid row
+    for (int i = tid; i < ET * ACT_S; i += NWAVES * WAVE)
+      lds[ACT_OFF + i] = __int_as_float(0);
   }
   __syncthreads();
 
@@ -405,6 +445,31 @@ __global__ void rollout_kernel(RolloutArgs a) {
           if (lane == 0) lds[ACT_OFF + e * ACT_S] = __int_as_float(arg);
         }
       }
+    } else if constexpr (FAM == FAM_MCAT) {
+      // thread = (env, component): Gumbel-max over the component's own
+      // logit range in LDS (independent draws per global column), then the
+      // per-env epsilon overlay.  Every tile slot is sampled, as above.
+      const int e = tid / MAX_A;   // 8 groups x 32 components
+      const int c = tid % MAX_A;
+      if (!(a.ablate & 4) && e < ET && c < A) {
+        const int ge = e0 + e;
+        const int off = a.moff[c], n = a.moff[c + 1] - off;
+        int arg = mcat_draw(
+            [&](int col) { return lds[PD_OFF + e * PD_S + col]; }, off, n,
+            a.seed, ge, step);
+        arg = mcat_explore(arg, n, c, a.seed, ge, step, a.eps_explore);
+        lds[ACT_OFF + e * ACT_S + c] = __int_as_float(arg);
+      }
+    } else if constexpr (FAM == FAM_BERN) {
+      const int e = tid / MAX_A;   // 8 groups x 32 dims
+      const int j = tid % MAX_A;
+      if (!(a.ablate & 4) && e < nE && j < A) {
+        const int ge = e0 + e;
+        const float act =
+            bern_draw(lds[PD_OFF + e * PD_S + j], a.seed, ge, step, j);
+        lds[ACT_OFF + e * ACT_S + j] =
+            bern_explore(act, j, a.seed, ge, step, a.eps_explore);
+      }
     } else if (!(a.ablate & 4)) {
       const int e = tid / MAX_A;   // 8 groups x 32 dims
       const int j = tid % MAX_A;
@@ -433,7 +498,7 @@ __global__ void rollout_kernel(RolloutArgs a) {
       for (int e = 0; e < nE; ++e) {
         const int64_t row = (int64_t)step * E + e0 + e;
         if (tid < P) out_pdflats[row * P + tid] = lds[PD_OFF + e * PD_S + tid];
-        if constexpr (FAM == FAM_BOX) {
+        if constexpr (FAM == FAM_BOX || FAM == FAM_BERN) {
           if (tid < A)
             out_actions[row * A + tid] = lds[ACT_OFF + e * ACT_S + tid];
         }
@@ -442,6 +507,13 @@ __global__ void rollout_kernel(RolloutArgs a) {
         if (tid < nE)
           reinterpret_cast<int64_t*>(a.out)[(int64_t)step * E + e0 + tid] =
               __float_as_int(lds[ACT_OFF + tid * ACT_S]);
+      }
+      if constexpr (FAM == FAM_MCAT) {
+        const int e = tid / MAX_A, c = tid % MAX_A;
+        if (e < nE && c < A)
+          reinterpret_cast<int64_t*>(
+              a.out)[((int64_t)step * E + e0 + e) * A + c] =
+              __float_as_int(lds[ACT_OFF + e * ACT_S + c]);
       }
       if (tid < nE) out_values[(int64_t)step * E + e0 + tid] = val_lds[tid];
     }
@@ -500,7 +572,19 @@ __global__ void rollout_kernel(RolloutArgs a) {
           for (int e = 0; e < ET; ++e)
             ain[e] = env_B[(int64_t)__float_as_int(lds[ACT_OFF + e * ACT_S]) *
                                D + d];
-        } else {  // Box: a_in = act @ B (body kept at the outer indent)
+        } else if constexpr (FAM == FAM_MCAT) {
+          // a_in = sum_c B[off_c + a_c][:], ascending c: C coalesced row
+          // gathers per env (lane == d), the eager index_select(...).sum(1)
+          for (int c = 0; c < A; ++c) {
+            const int off = a.moff[c];
+            #pragma unroll
+            for (int e = 0; e < ET; ++e)
+              ain[e] += env_B[(int64_t)(off + __float_as_int(
+                                            lds[ACT_OFF + e * ACT_S + c])) *
+                                  D + d];
+          }
+        } else {  // Box, Bernoulli: a_in = act @ B (body kept at the outer
+                  // indent)
         int j = 0;
         for (; j + 4 <= A; j += 4) {
           const float b0 = env_B[(int64_t)(j + 0) * D + d];
@@ -986,6 +1070,39 @@ std::vector<torch::Tensor> rollout_run(
   return {states, pdflats, actions, values, rewards, dones, boot_v, moments};
 }
 
+// Launch selection of the runtime-shape logit families (FAM_CAT, FAM_MCAT,
+// FAM_BERN), following rollout_run: min-waves 1 for grids within one block
+// per CU, else 4, unless DPPO_ROLLOUT_MW picks; 2- or 8-env tiles.
+template <int FAM>
+static void launch_rollout_fam(const RolloutArgsOf<FAM>& a, int grid, int et,
+                               size_t lds_bytes, hipStream_t stream) {
+  const int mw_env = rollout_mw_env();
+  const int mw = mw_env >= 0 ? mw_env : (grid <= N_CU ? 1 : 4);
+  const dim3 g(grid), b(NWAVES * WAVE);
+  if (mw >= 4) {
+    if (et == 2)
+      hipLaunchKernelGGL((rollout_kernel<4, 2, 0, 0, 0, 0, 0, 0, FAM>), g, b,
+                         lds_bytes, stream, a);
+    else
+      hipLaunchKernelGGL((rollout_kernel<4, 8, 0, 0, 0, 0, 0, 0, FAM>), g, b,
+                         lds_bytes, stream, a);
+  } else if (mw >= 2) {
+    if (et == 2)
+      hipLaunchKernelGGL((rollout_kernel<3, 2, 0, 0, 0, 0, 0, 0, FAM>), g, b,
+                         lds_bytes, stream, a);
+    else
+      hipLaunchKernelGGL((rollout_kernel<3, 8, 0, 0, 0, 0, 0, 0, FAM>), g, b,
+                         lds_bytes, stream, a);
+  } else {
+    if (et == 2)
+      hipLaunchKernelGGL((rollout_kernel<1, 2, 0, 0, 0, 0, 0, 0, FAM>), g, b,
+                         lds_bytes, stream, a);
+    else
+      hipLaunchKernelGGL((rollout_kernel<1, 8, 0, 0, 0, 0, 0, 0, FAM>), g, b,
+                         lds_bytes, stream, a);
+  }
+}
+
 // Discrete/Categorical whole-rollout: the FAM_CAT instantiations of
 // rollout_kernel (K logits + value heads, Gumbel-max sampling, uniform-index
 // epsilon overlay, a_in = B[a] row gather, int64 action indices written by
@@ -1042,31 +1159,7 @@ std::vector<torch::Tensor> rollout_run_cat(
       (et * (r4((int)D) + 2 * r4(h_max) + r4(K) + r4(1) + r4((int)rank) + 4) +
        NWAVES * et * r4(std::max(h_max, K + 1))) *
       sizeof(float);
-  const int mw_env = rollout_mw_env();
-  const int mw = mw_env >= 0 ? mw_env : (grid <= N_CU ? 1 : 4);
-  const dim3 g(grid), b(NWAVES * WAVE);
-  if (mw >= 4) {
-    if (et == 2)
-      hipLaunchKernelGGL((rollout_kernel<4, 2, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
-                         b, lds_bytes, stream, a);
-    else
-      hipLaunchKernelGGL((rollout_kernel<4, 8, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
-                         b, lds_bytes, stream, a);
-  } else if (mw >= 2) {
-    if (et == 2)
-      hipLaunchKernelGGL((rollout_kernel<3, 2, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
-                         b, lds_bytes, stream, a);
-    else
-      hipLaunchKernelGGL((rollout_kernel<3, 8, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
-                         b, lds_bytes, stream, a);
-  } else {
-    if (et == 2)
-      hipLaunchKernelGGL((rollout_kernel<1, 2, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
-                         b, lds_bytes, stream, a);
-    else
-      hipLaunchKernelGGL((rollout_kernel<1, 8, 0, 0, 0, 0, 0, 0, FAM_CAT>), g,
-                         b, lds_bytes, stream, a);
-  }
+  launch_rollout_fam<FAM_CAT>(a, grid, et, lds_bytes, stream);
 
   auto actions = out.narrow(0, 0, 2 * T * E).view(torch::kInt64).view({T, E});
   int64_t o = 2 * T * E;
@@ -1093,6 +1186,145 @@ std::vector<torch::Tensor> rollout_run_cat(
   hipLaunchKernelGGL(ep_moments_decode_kernel, dim3(1), dim3(1), 0, stream,
                      moments.data_ptr<float>());
   return {states, pdflats, actions, values, rewards, dones, boot_v, moments};
+}
+
+// MultiDiscrete/MultiCategorical (FAM_MCAT: act_w = C components, moff =
+// their first logit columns + P) and MultiBinary/Bernoulli (FAM_BERN: act_w
+// = P = n) whole-rollout, after rollout_run_cat: P logits + value heads,
+// per-family sampler and epsilon overlay, a_in = sum_c B[off_c + a_c] or
+// act @ B.  The family limits are checked by the two callers below.
+template <int FAM>
+static std::vector<torch::Tensor> rollout_run_multi(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation,
+    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
+    double noise, double eps_explore,
+    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
+    int64_t T, int64_t act_w, int64_t P, const std::vector<int>& moff,
+    int64_t seed, torch::Tensor out_buf, int64_t ablate) {
+  const int64_t E = x.size(0);
+  const int64_t D = x.size(1);
+  RolloutArgsOf<FAM> a{};
+  static_cast<RolloutArgs&>(a) =
+      rollout_args(params, offsets, dims, activation, envblob, rank, horizons,
+                   noise, 0.0, 0.0, eps_explore, x, t, epr, T, act_w, seed,
+                   ablate);
+  if constexpr (FAM == FAM_MCAT)
+    for (size_t c = 0; c < moff.size(); ++c) a.moff[c] = moff[c];
+  const int h_max = a.h_max;
+  TORCH_CHECK(T >= 1 && E >= 1 && params.is_cuda());
+  TORCH_CHECK(envblob.is_cuda() && envblob.is_contiguous() &&
+                  envblob.dtype() == torch::kFloat32 &&
+                  envblob.numel() == D + 2 * rank * D + P * D,
+              "env blob must be d | Vt[r][D] | U[r][D] | B[P][D]");
+  TORCH_CHECK(horizons.numel() == E && t.numel() == E && epr.numel() == E);
+  TORCH_CHECK(horizons.is_cuda() && t.is_cuda() && epr.is_cuda() &&
+              epr.dtype() == torch::kFloat32);
+  TORCH_CHECK(params.numel() >=
+                  offsets[2 * a.n_hidden + 2] + (int64_t)dims.back() * P &&
+                  params.numel() >= offsets[2 * a.n_hidden + 3] + P,
+              "weight blob too small for the P-wide policy head");
+
+  // FAM_MCAT blob: actions(int64)[T*E*C] | states | logits | values |
+  // rewards | dones | boot | moments, in floats (the int64 region is
+  // 2*T*E*C floats wide and leads the blob so it is 8-byte aligned).
+  // FAM_BERN: Box's layout, states | logits | actions | values | ...
+  const int64_t n_out = (FAM == FAM_MCAT)
+                            ? T * E * (2 * act_w + D + P + 3) + E + 5
+                            : T * E * (D + P + act_w + 3) + E + 5;
+  torch::Tensor out = (out_buf.numel() == n_out)
+                          ? out_buf
+                          : torch::empty({n_out}, x.options());
+  TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kFloat32 &&
+              out.is_contiguous());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr<float>()) % 8 == 0,
+              "rollout output blob must be 8-byte aligned");
+  auto epr_in = epr.clone();
+  a.out = out.data_ptr<float>();
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  const int et = ((E + ENV_TILE - 1) / ENV_TILE < 128 && E % 2 == 0) ? 2
+                                                                     : ENV_TILE;
+  const int grid = static_cast<int>((E + et - 1) / et);
+  auto r4 = [](int v) { return (v + 3) & ~3; };
+  // mirrors the kernel's lds_map for these families
+  const size_t lds_bytes =
+      (et * (r4((int)D) + 2 * r4(h_max) + r4((int)P) + r4((int)act_w) +
+             r4((int)rank) + 4) +
+       NWAVES * et * r4(std::max(h_max, (int)P + 1))) *
+      sizeof(float);
+  launch_rollout_fam<FAM>(a, grid, et, lds_bytes, stream);
+
+  int64_t o = 0;
+  auto take = [&](std::vector<int64_t> shape) {
+    int64_t n = 1;
+    for (auto sdim : shape) n *= sdim;
+    auto v = out.narrow(0, o, n).view(shape);
+    o += n;
+    return v;
+  };
+  torch::Tensor actions;
+  if (FAM == FAM_MCAT) {
+    actions = out.narrow(0, 0, 2 * T * E * act_w)
+                  .view(torch::kInt64)
+                  .view({T, E, act_w});
+    o = 2 * T * E * act_w;
+  }
+  // (typed: the lambda's result is a dependent type in this template)
+  torch::Tensor states = take({T, E, D});
+  torch::Tensor pdflats = take({T, E, P});
+  if (FAM == FAM_BERN) actions = take({T, E, act_w});
+  torch::Tensor values = take({T, E});
+  torch::Tensor rewards = take({T, E});
+  torch::Tensor dones = take({T, E});
+  torch::Tensor boot_v = take({E});
+  torch::Tensor moments = take({5});
+  moments.zero_();
+
+  hipLaunchKernelGGL(ep_moments_kernel,
+                     dim3(static_cast<int>((E + 255) / 256)), dim3(256), 0,
+                     stream, rewards.data_ptr<float>(), dones.data_ptr<float>(),
+                     epr_in.data_ptr<float>(), moments.data_ptr<float>(), T, E);
+  hipLaunchKernelGGL(ep_moments_decode_kernel, dim3(1), dim3(1), 0, stream,
+                     moments.data_ptr<float>());
+  return {states, pdflats, actions, values, rewards, dones, boot_v, moments};
+}
+
+std::vector<torch::Tensor> rollout_run_mcat(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation,
+    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
+    double noise, double eps_explore,
+    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
+    int64_t T, std::vector<int64_t> nvec, int64_t seed, torch::Tensor out_buf,
+    int64_t ablate) {
+  TORCH_CHECK(!nvec.empty() && nvec.size() <= (size_t)MAX_A,
+              "multi-categorical rollout supports 1..32 components");
+  std::vector<int> moff{0};
+  for (int64_t n : nvec) {
+    TORCH_CHECK(n >= 2, "multi-categorical rollout needs every n_c >= 2");
+    TORCH_CHECK(moff.back() + n <= MAX_K,
+                "multi-categorical rollout supports sum(nvec) <= 64");
+    moff.push_back(moff.back() + static_cast<int>(n));
+  }
+  return rollout_run_multi<FAM_MCAT>(
+      params, offsets, dims, activation, envblob, rank, horizons, noise,
+      eps_explore, x, t, epr, T, (int64_t)nvec.size(), moff.back(), moff, seed,
+      out_buf, ablate);
+}
+
+std::vector<torch::Tensor> rollout_run_bern(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation,
+    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
+    double noise, double eps_explore,
+    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
+    int64_t T, int64_t n, int64_t seed, torch::Tensor out_buf,
+    int64_t ablate) {
+  TORCH_CHECK(n >= 1 && n <= MAX_A, "bernoulli rollout supports 1 <= n <= 32");
+  return rollout_run_multi<FAM_BERN>(
+      params, offsets, dims, activation, envblob, rank, horizons, noise,
+      eps_explore, x, t, epr, T, n, n, {}, seed, out_buf, ablate);
 }
 
 void rollout_sample(torch::Tensor pdflat, torch::Tensor actions,

@@ -1,9 +1,11 @@
-// Shared rollout device math: the counter RNG, its slot scheme, Box action
-// sampling, the synthetic env transition and the per-env episode step.
+// Shared rollout device math: the counter RNG, its slot scheme, Box,
+// MultiCategorical and Bernoulli action sampling, the synthetic env
+// transition and the per-env episode step.
 // rollout.hip (whole-rollout kernel, sample_kernel, env_finish_kernel),
 // mfma_gemm.hip (fused env-step epilogue, fused policy forward,
-// env_finish2_kernel) and cat_loss.hip (Gumbel-max sampler) all take them
-// from here, so the paths that must agree bitwise run the same expressions.
+// env_finish2_kernel), cat_loss.hip (Gumbel-max sampler) and multi_loss.hip
+// (mcat_sample, bern_sample) all take them from here, so the paths that must
+// agree bitwise run the same expressions.
 #pragma once
 
 #include "common.h"
@@ -12,7 +14,10 @@
 // Stateless: a draw is a hash of (seed, env, step, slot).  Slot scheme, per
 // (env, step):
 //   j                 action draw of dim / class j (Box: normal, .x of the
-//                     pair; Categorical: the Gumbel uniform)
+//                     pair; Categorical: the Gumbel uniform;
+//                     MultiCategorical: the Gumbel uniform of GLOBAL logit
+//                     column j = off_c + class, so components never share
+//                     a draw; Bernoulli: the uniform compared to sigmoid)
 //   RNG_SLOT_ENV + s  env transition noise, one Box-Muller PAIR per slot:
 //                     - whole-rollout kernel: s = d, the pair drawn for the
 //                       EVEN env of a pair feeds dim d of envs 2q and 2q+1;
@@ -24,7 +29,10 @@
 //                     them to share trajectories.
 //   RNG_SLOT_RESET + d   reset state of dim d (0.1 * normal, .x of the pair)
 //   RNG_SLOT_EPS         epsilon-greedy decision (uniform < eps)
-//   RNG_SLOT_EPS_ACT + j epsilon-greedy action draw (Categorical: j = 0)
+//   RNG_SLOT_EPS_ACT + j epsilon-greedy action draw (Categorical: j = 0;
+//                        MultiCategorical: j = component; Bernoulli: j = dim)
+// The stand-alone samplers (cat_sample, mcat_sample, bern_sample) use the
+// action slots with env = batch row and step = the caller's counter.
 // Within the per-step path every kernel uses the same slots, so the split
 // launches (sample_kernel, env_finish_kernel) and the fused ones
 // (mlp_fwd_fused_kernel, gemm_fwd_glds_kernel<*, true>) sample the same
@@ -86,6 +94,58 @@ DEV_INLINE float box_sample(float mean, float logstd, unsigned seed,
         rng_uniform(seed, (int)env, step, RNG_SLOT_EPS_ACT + j);
     act = low + (high - low) * u;
   }
+  return act;
+}
+
+// ---- MultiCategorical action: Gumbel-max per component --------------------
+// argmax_j(logit_j - log(-log u_j)) over the n logits of one component that
+// starts at global column `off`; logit_at(col) reads a logit (LDS in the
+// rollout kernel, global memory in mcat_sample_kernel).  Ties and non-finite
+// scores go to the lowest index; -log u is floored at 2^-24 as in the
+// Categorical rollout, so the draw is finite for u == 1.
+template <class LogitAt>
+DEV_INLINE int mcat_draw(LogitAt logit_at, int off, int n, unsigned seed,
+                         int env, int step) {
+  float best = -3.0e38f;
+  int arg = 0;
+  for (int j = 0; j < n; ++j) {
+    const float nl = fmaxf(-__logf(rng_uniform(seed, env, step, off + j)),
+                           5.9604645e-8f);
+    const float gv = logit_at(off + j) - __logf(nl);
+    if (gv > best) {
+      best = gv;
+      arg = j;
+    }
+  }
+  return arg;
+}
+
+// epsilon-greedy overlay of component c (n classes): ONE decision per
+// (env, step); an explored env redraws every component uniformly.  The
+// result is clamped into [0, n-1] (u == 1 gives n).
+DEV_INLINE int mcat_explore(int arg, int n, int c, unsigned seed, int env,
+                            int step, float eps) {
+  if (rng_uniform(seed, env, step, RNG_SLOT_EPS) < eps)
+    arg = (int)(rng_uniform(seed, env, step, RNG_SLOT_EPS_ACT + c) * n);
+  return max(0, min(n - 1, arg));
+}
+
+// ---- Bernoulli action ------------------------------------------------------
+// a_j = (u_j <= sigmoid(l_j)): u is in (0, 1], so `<=` makes a saturated head
+// (p rounds to 1) always give 1, and p == 0 never does.
+DEV_INLINE float bern_draw(float logit, unsigned seed, int env, int step,
+                           int j) {
+  const float p = 1.f / (1.f + __expf(-logit));
+  return (rng_uniform(seed, env, step, j) <= p) ? 1.f : 0.f;
+}
+
+// epsilon-greedy overlay of dim j: one decision per (env, step), explored
+// dims are Bernoulli(0.5)
+DEV_INLINE float bern_explore(float act, int j, unsigned seed, int env,
+                              int step, float eps) {
+  if (rng_uniform(seed, env, step, RNG_SLOT_EPS) < eps)
+    act = (rng_uniform(seed, env, step, RNG_SLOT_EPS_ACT + j) < 0.5f) ? 1.f
+                                                                     : 0.f;
   return act;
 }
 

@@ -16,8 +16,8 @@ the Adam learning rate and the clip range (reference PPO.py:19-20).
 
 The eager path below is the autograd reference; the fused HIP kernels
 (ops/hip/ppo_loss.hip for DiagGaussian, ops/hip/cat_loss.hip for
-Categorical — the reference's default family, distributions.py:124-159)
-each compute the whole thing — logp for pi and oldpi, ratio, both clips,
+Categorical — the reference's default family, distributions.py:124-159 —
+and ops/hip/multi_loss.hip for MultiCategorical and Bernoulli) each compute the whole thing — logp for pi and oldpi, ratio, both clips,
 entropy, and the three block-reduced means — in one forward kernel and
 one analytic backward kernel, and are tested against this path to
 tolerance.
@@ -30,7 +30,8 @@ from typing import Dict
 
 import torch
 
-from ..distributions import Pd, DiagGaussianPd, CategoricalPd
+from ..distributions import (
+    BernoulliPd, CategoricalPd, DiagGaussianPd, MultiCategoricalPd, Pd)
 
 
 @dataclass
@@ -154,6 +155,61 @@ class _FusedPPOLossCategorical(torch.autograd.Function):
         return (g_logits, None, g_v) + (None,) * 7
 
 
+class _FusedPPOLossMultiCategorical(torch.autograd.Function):
+    """Fused MultiCategorical PPO loss (ops/hip/multi_loss.hip): per
+    component the Categorical math, logp and entropy summed over components
+    (reference distributions.py:161-182).  `nvec` is the tuple of component
+    sizes; gradients flow to the pi logits and vpred only."""
+
+    @staticmethod
+    def forward(ctx, logits_pi, logits_old, vpred, oldvpred, actions, adv,
+                etr, nvec, clip_param, entcoeff, vcoeff):
+        from . import require_hip_ext
+
+        ext = require_hip_ext()
+        saved = tuple(t.contiguous() for t in (
+            logits_pi, logits_old, vpred, oldvpred, actions, adv, etr))
+        ctx.args = (list(nvec), float(clip_param), float(entcoeff),
+                    float(vcoeff))
+        ctx.save_for_backward(*saved)
+        return ext.ppo_loss_mcat_fwd(*saved, *ctx.args)
+
+    @staticmethod
+    def backward(ctx, grad_losses):
+        from . import require_hip_ext
+
+        g_logits, g_v = require_hip_ext().ppo_loss_mcat_bwd(
+            *ctx.saved_tensors, *ctx.args, grad_losses[3])
+        return (g_logits, None, g_v) + (None,) * 8
+
+
+class _FusedPPOLossBernoulli(torch.autograd.Function):
+    """Fused Bernoulli PPO loss (ops/hip/multi_loss.hip): stable-softplus
+    neglogp and entropy summed over dims (reference
+    distributions.py:210-229).  Gradients flow to the pi logits and vpred
+    only."""
+
+    @staticmethod
+    def forward(ctx, logits_pi, logits_old, vpred, oldvpred, actions, adv,
+                etr, clip_param, entcoeff, vcoeff):
+        from . import require_hip_ext
+
+        ext = require_hip_ext()
+        saved = tuple(t.contiguous() for t in (
+            logits_pi, logits_old, vpred, oldvpred, actions, adv, etr))
+        ctx.args = (float(clip_param), float(entcoeff), float(vcoeff))
+        ctx.save_for_backward(*saved)
+        return ext.ppo_loss_bern_fwd(*saved, *ctx.args)
+
+    @staticmethod
+    def backward(ctx, grad_losses):
+        from . import require_hip_ext
+
+        g_logits, g_v = require_hip_ext().ppo_loss_bern_bwd(
+            *ctx.saved_tensors, *ctx.args, grad_losses[3])
+        return (g_logits, None, g_v) + (None,) * 7
+
+
 def _loss_dict(losses: torch.Tensor) -> Dict[str, torch.Tensor]:
     return {
         "policyLoss": losses[0],
@@ -174,8 +230,9 @@ def ppo_losses(
     coeffs: PPOLossCoeffs,
     policy: str = "auto",
 ) -> Dict[str, torch.Tensor]:
-    """PPO losses with fused-HIP dispatch for DiagGaussian and Categorical
-    policies (the other families run the eager reference)."""
+    """PPO losses with fused-HIP dispatch for the four policy families,
+    within the column limits of their kernels (anything else runs the eager
+    reference)."""
     from . import use_hip
 
     if (
@@ -197,6 +254,31 @@ def ppo_losses(
         return _loss_dict(_FusedPPOLossCategorical.apply(
             pd.flatparam(), oldpd.flatparam().detach(),
             vpred, oldvpred.detach(), actions.long(), adv, etr,
+            coeffs.clip_param, coeffs.entcoeff, coeffs.vcoeff,
+        ))
+    if (
+        isinstance(pd, MultiCategoricalPd)
+        and isinstance(oldpd, MultiCategoricalPd)
+        and pd.nvec == oldpd.nvec
+        and sum(pd.nvec) <= 64  # one wave covers the columns
+        and pd.flatparam().dim() == 2
+        and use_hip(vpred, policy)
+    ):
+        return _loss_dict(_FusedPPOLossMultiCategorical.apply(
+            pd.flatparam(), oldpd.flatparam().detach(),
+            vpred, oldvpred.detach(), actions.long(), adv, etr, pd.nvec,
+            coeffs.clip_param, coeffs.entcoeff, coeffs.vcoeff,
+        ))
+    if (
+        isinstance(pd, BernoulliPd)
+        and isinstance(oldpd, BernoulliPd)
+        and pd.flatparam().dim() == 2
+        and pd.flatparam().shape[-1] <= 64
+        and use_hip(vpred, policy)
+    ):
+        return _loss_dict(_FusedPPOLossBernoulli.apply(
+            pd.flatparam(), oldpd.flatparam().detach(),
+            vpred, oldvpred.detach(), actions.to(vpred.dtype), adv, etr,
             coeffs.clip_param, coeffs.entcoeff, coeffs.vcoeff,
         ))
     return ppo_losses_ref(pd, oldpd, vpred, oldvpred, actions, adv, etr, coeffs)

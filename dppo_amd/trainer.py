@@ -111,7 +111,7 @@ class DPPOEngine:
         # Lazily created state, declared here with its "unset" value:
         self._warned = set()            # _warn_once keys already printed
         self._wide_path = None          # WideBF16Path (ops/wide.py)
-        self._cat_ctr = 0               # cat_sample RNG counter
+        self._sample_ctr = 0            # cat/mcat/bern_sample RNG counter
         self._rollout_counter = 0       # rollout seed counter
         # persistent rollout / GAE outputs (stable addresses for capture)
         self._rollout_out = self._adv_buf = self._etr_buf = None
@@ -332,16 +332,25 @@ class DPPOEngine:
 
         v, pdflat = self._policy_forward(obs)
         pd = self.pi.pdtype.pdfromflat(pdflat)
-        if (self._discrete and pdflat.shape[-1] <= 64
+        kind = self._act_kind
+        if (((kind in ("discrete", "multidiscrete")
+              and pdflat.shape[-1] <= 64) or kind == "multibinary")
                 and use_hip(self.device, self.cfg.USE_HIP_KERNELS)):
-            # fused Gumbel-max sample kernel (cat_loss.hip) — counter-based
-            # RNG, one launch, no torch RNG round trips
+            # fused sample kernels (cat_loss.hip: Gumbel-max; multi_loss.hip:
+            # Gumbel-max per component, Bernoulli) — counter-based RNG, one
+            # launch, no torch RNG round trips
             from .ops import hip_ext
 
-            self._cat_ctr += 1
+            self._sample_ctr += 1
             seed = (self.cfg.SEED * 1_000_003
                     + self.comm.rank * 7_919) & 0x7FFFFFFF
-            a = hip_ext().cat_sample(pdflat, seed, self._cat_ctr)
+            if kind == "discrete":
+                a = hip_ext().cat_sample(pdflat, seed, self._sample_ctr)
+            elif kind == "multidiscrete":
+                a = hip_ext().mcat_sample(
+                    pdflat, self._nvec, seed, self._sample_ctr)
+            else:
+                a = hip_ext().bern_sample(pdflat, seed, self._sample_ctr)
         else:
             a = pd.sample()
         if eps > 0.0:
@@ -376,6 +385,8 @@ class DPPOEngine:
             return self._rollout_once_hip()
         if self._use_rollout_cat():
             return self._rollout_once_hip_cat()
+        if self._use_rollout_multi():
+            return self._rollout_once_hip_multi()
         return self._rollout_once_eager()
 
     def _can_fuse_rollout_cat(self) -> bool:
@@ -409,6 +420,52 @@ class DPPOEngine:
         # 28.0 / 27.8 ms vs fused 0.54 / 1.22 / 9.78 ms; repeat spread < 1 %
         # on the fused arm.  No crossover in the measured range -> on
         # wherever eligible.
+        return True
+
+    @property
+    def _nvec(self):
+        """Component sizes of a MultiDiscrete action space."""
+        return [int(n) for n in self.act_space.nvec]
+
+    def _can_fuse_rollout_multi(self) -> bool:
+        """Eligibility for the MultiCategorical / Bernoulli instantiations of
+        the fused HIP rollout kernel (rollout.hip, rollout_run_mcat /
+        rollout_run_bern): MultiDiscrete with every n_c >= 2 and
+        sum(nvec) <= 64, or MultiBinary with n <= 32; dims within kernel
+        limits, fp32, GPU.  Its own function: _can_fuse_rollout_cat() stays
+        False for these games."""
+        c = self.cfg
+        if not (self._hip_path("multidiscrete")
+                or self._hip_path("multibinary")):
+            return False
+        if not (1 <= len(c.HIDDEN_SIZES) <= 3):
+            return False
+        if max(c.HIDDEN_SIZES) > 128 or self.obs_space.shape[0] > 512:
+            return False
+        if self.env.Vt.size(0) > 32:
+            return False
+        if self._act_kind == "multidiscrete":
+            nvec = self._nvec
+            return (1 <= len(nvec) <= 32 and min(nvec) >= 2
+                    and sum(nvec) <= 64)
+        return 1 <= self.act_space.n <= 32
+
+    def _use_rollout_multi(self) -> bool:
+        """Dispatch for MultiDiscrete / MultiBinary games:
+        DPPO_ROLLOUT_MULTI=0 forces the eager loop, any other value the
+        fused kernel wherever eligible."""
+        if not self._can_fuse_rollout_multi():
+            return False
+        ov = os.environ.get("DPPO_ROLLOUT_MULTI")
+        if ov is not None:
+            return ov != "0"
+        # measured, T=64 (tools/rollout_multi_ab.py,
+        # profiles/r10_rollout_multi.txt): MultiLever (32,) eager 32.8 / 34.7 /
+        # 31.9 ms vs fused 0.50 / 1.10 / 8.56 ms at E = 128 / 4096 / 65536;
+        # BitFlipper (64,64) eager 30.1 / 30.4 / 32.5 ms vs fused 0.53 / 1.25 /
+        # 9.92 ms; the widest min..max spread is 6.6 ms (eager) and 0.04 ms
+        # (fused).  No crossover in the measured range -> on wherever
+        # eligible.
         return True
 
     def _can_rollout_v3(self) -> bool:
@@ -459,7 +516,7 @@ class DPPOEngine:
         """One rollout iteration in a single fused kernel launch
         (ops/hip/rollout.hip): MLP forward + sampling + epsilon-greedy +
         env dynamics + episode bookkeeping for all T steps."""
-        return self._rollout_once_fused(cat=False)
+        return self._rollout_once_fused("box")
 
     @torch.no_grad()
     def _rollout_once_hip_cat(self) -> Tuple[RolloutBatch, Dict[str, float]]:
@@ -467,7 +524,16 @@ class DPPOEngine:
         Categorical instantiation of rollout.hip): MLP forward + Gumbel-max
         sampling + epsilon-greedy + env dynamics + episode bookkeeping for
         all T steps; int64 action indices come straight from the kernel."""
-        return self._rollout_once_fused(cat=True)
+        return self._rollout_once_fused("discrete")
+
+    @torch.no_grad()
+    def _rollout_once_hip_multi(self) -> Tuple[RolloutBatch, Dict[str, float]]:
+        """MultiDiscrete / MultiBinary rollout in a single fused kernel
+        launch (the MultiCategorical / Bernoulli instantiations of
+        rollout.hip): per-component Gumbel-max or Bernoulli sampling, the
+        per-env epsilon overlay, a_in = sum_c B[off_c + a_c] or act @ B;
+        int64 [C] or float 0/1 [n] actions come straight from the kernel."""
+        return self._rollout_once_fused(self._act_kind)
 
     def _next_rollout_seed(self) -> int:
         """Seed of the next HIP rollout: SEED, rank and a per-engine
@@ -494,9 +560,10 @@ class DPPOEngine:
         return (float(self.act_space.low.flat[0]),
                 float(self.act_space.high.flat[0]))
 
-    def _rollout_once_fused(self, cat: bool):
-        """The single-launch rollout of either policy family: Categorical
-        (`cat`) or DiagGaussian, which also takes the action bounds."""
+    def _rollout_once_fused(self, kind: str):
+        """The single-launch rollout of one policy family (`kind`, an
+        _act_kind): Categorical, MultiCategorical, Bernoulli or DiagGaussian,
+        which also takes the action bounds."""
         from .ops import hip_ext
 
         ext = hip_ext()
@@ -507,12 +574,22 @@ class DPPOEngine:
         seed = self._next_rollout_seed()
         blob, offsets, dims = self._rollout_weight_blob()
         D = self.obs_space.shape[0]
-        if cat:
+        if kind == "discrete":
             n_act = self.act_space.n
             # actions(int64) | states | logits | values | rewards | dones |
             # boot | moments, in floats
             n_out = T * E * (2 + D + n_act + 3) + E + 5
             run, bounds = ext.rollout_run_cat, ()
+        elif kind == "multidiscrete":
+            n_act = self._nvec
+            # as above with C int64 actions and sum(nvec) logits per row
+            n_out = T * E * (2 * len(n_act) + D + sum(n_act) + 3) + E + 5
+            run, bounds = ext.rollout_run_mcat, ()
+        elif kind == "multibinary":
+            n_act = self.act_space.n
+            # Box's layout with n logits: states | logits | actions | ...
+            n_out = T * E * (D + 2 * n_act + 3) + E + 5
+            run, bounds = ext.rollout_run_bern, ()
         else:
             n_act = self.act_space.shape[0]
             n_out = T * E * (D + 3 * n_act + 3) + E + 5
