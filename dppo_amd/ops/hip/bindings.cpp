@@ -207,7 +207,42 @@ torch::Tensor mcat_sample(torch::Tensor logits, std::vector<int64_t> nvec,
 
 torch::Tensor bern_sample(torch::Tensor logits, int64_t seed, int64_t ctr);
 
+torch::Tensor ppo_loss_cat_gh(torch::Tensor lpi, torch::Tensor lold,
+                              torch::Tensor vpred, torch::Tensor oldv,
+                              torch::Tensor act, torch::Tensor adv,
+                              torch::Tensor etr, double clip, double entcoeff,
+                              double vcoeff, torch::Tensor clip_dev);
+
+torch::Tensor ppo_loss_mcat_gh(torch::Tensor lpi, torch::Tensor lold,
+                               torch::Tensor vpred, torch::Tensor oldv,
+                               torch::Tensor act, torch::Tensor adv,
+                               torch::Tensor etr, std::vector<int64_t> nvec,
+                               double clip, double entcoeff, double vcoeff,
+                               torch::Tensor clip_dev);
+
+torch::Tensor ppo_loss_bern_gh(torch::Tensor lpi, torch::Tensor lold,
+                               torch::Tensor vpred, torch::Tensor oldv,
+                               torch::Tensor act, torch::Tensor adv,
+                               torch::Tensor etr, double clip, double entcoeff,
+                               double vcoeff, torch::Tensor clip_dev);
+
+int64_t ppo_gh_disc_tile(int64_t P, int64_t act_width);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("ppo_loss_cat_gh", &ppo_loss_cat_gh,
+          "Categorical PPO loss gradient -> gh [B][ldgh] = [g_logits | g_v | "
+          "0], int64 actions [B]; layout: ops.ppo_loss.ppo_gh_ref (gfx950)");
+  mod.def("ppo_loss_mcat_gh", &ppo_loss_mcat_gh,
+          "MultiCategorical PPO loss gradient -> gh [B][ldgh] = [g_logits | "
+          "g_v | 0], int64 actions [B][C]; layout: ops.ppo_loss.ppo_gh_ref "
+          "(gfx950)");
+  mod.def("ppo_loss_bern_gh", &ppo_loss_bern_gh,
+          "Bernoulli PPO loss gradient -> gh [B][ldgh] = [g_logits | g_v | "
+          "0], float 0/1 actions [B][n]; layout: ops.ppo_loss.ppo_gh_ref "
+          "(gfx950)");
+  mod.def("ppo_gh_disc_tile", &ppo_gh_disc_tile,
+          "rows per block of the ppo_loss_{cat,mcat,bern}_gh kernels for P "
+          "logit and act_width action columns");
   mod.def("rollout_run_mcat", &rollout_run_mcat,
           "fused T-step rollout, MultiDiscrete/MultiCategorical policy: MLP "
           "fwd + per-component Gumbel-max + synthetic env, int64 actions "

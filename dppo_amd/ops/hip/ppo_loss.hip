@@ -21,47 +21,10 @@
 #include <c10/hip/HIPStream.h>
 
 #include "common.h"
+#include "gh_tile.h"
 #include "ppo_math.h"
 
 namespace {
-
-// Stage a [rows][width] contiguous global stream into padded LDS rows.
-// Global side is float4 where width >= 8 (the caller guarantees the
-// base is 16-B aligned: tile_base*width is a multiple of 4), LDS side
-// is 4 scalar writes with an at-most-one row wrap per group.  row/col
-// kept by increment — one div/mod per stream, not per element.
-DEV_INLINE void stage_tile(const float* __restrict__ src,
-                           float* __restrict__ dst, int width, int stride,
-                           int rows, int tid) {
-  const int n = rows * width;
-  if (width >= 8) {
-    const float4* s4 = reinterpret_cast<const float4*>(src);
-    const int n4 = n >> 2;
-    const int dr = 1024 / width, dc = 1024 % width;
-    int r = (tid * 4) / width, c = (tid * 4) % width;
-    for (int q = tid; q < n4; q += 256) {
-      const float4 v = s4[q];
-      int rr = r, cc = c;
-      const float vv[4] = {v.x, v.y, v.z, v.w};
-      #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        dst[rr * stride + cc] = vv[k];
-        if (++cc == width) { cc = 0; ++rr; }
-      }
-      r += dr; c += dc;
-      if (c >= width) { c -= width; ++r; }
-    }
-    for (int g = (n4 << 2) + tid; g < n; g += 256)
-      dst[(g / width) * stride + g % width] = src[g];
-  } else {
-    const int dr = 256 / width, dc = 256 % width;
-    for (int g = tid, r = tid / width, c = tid % width; g < n; g += 256) {
-      dst[r * stride + c] = src[g];
-      r += dr; c += dc;
-      if (c >= width) { c -= width; r += 1; }
-    }
-  }
-}
 
 __launch_bounds__(256)
 __global__ void ppo_gauss_fwd_kernel(

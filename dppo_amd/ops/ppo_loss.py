@@ -72,6 +72,43 @@ def ppo_losses_ref(
     }
 
 
+def ppo_gh_ref(
+    pd: Pd,
+    oldpd: Pd,
+    vpred: torch.Tensor,
+    oldvpred: torch.Tensor,
+    actions: torch.Tensor,
+    adv: torch.Tensor,
+    etr: torch.Tensor,
+    coeffs: PPOLossCoeffs,
+) -> torch.Tensor:
+    """The update's loss-gradient operand `gh`, by autograd on
+    ppo_losses_ref: the definition of the layout the gh kernels write
+    (ppo_loss_gauss_gh, ppo_loss_{cat,mcat,bern}_gh).
+
+    gh is [B][ldgh] with P = pd.flatparam().shape[-1] and
+    ldgh = (P + 1 + 3) & ~3 (rows padded to a float4 multiple):
+        columns 0..P-1      d total_loss / d flatparam (upstream gradient 1,
+                            the 1/B of the means folded in)
+        column  P           d total_loss / d vpred
+        columns P+1..ldgh-1 zero
+    Runs on CPU and GPU in any float dtype."""
+    flat = pd.flatparam().detach().clone().requires_grad_(True)
+    v = vpred.detach().clone().requires_grad_(True)
+    if isinstance(pd, MultiCategoricalPd):
+        pd_leaf = MultiCategoricalPd(pd.nvec, flat)
+    else:
+        pd_leaf = type(pd)(flat)
+    total = ppo_losses_ref(pd_leaf, oldpd, v, oldvpred.detach(), actions,
+                           adv, etr, coeffs)["total_loss"]
+    g_flat, g_v = torch.autograd.grad(total, (flat, v))
+    B, P = flat.shape
+    gh = flat.new_zeros(B, (P + 1 + 3) & ~3)
+    gh[:, :P] = g_flat
+    gh[:, P] = g_v
+    return gh
+
+
 class _FusedPPOLossGaussian(torch.autograd.Function):
     """Fused DiagGaussian PPO loss: HIP forward + analytic HIP backward.
 

@@ -1322,23 +1322,66 @@ class DPPOEngine:
 
     # ------------------------------------------------------------------
     def _can_fuse_update(self) -> bool:
-        """Eligibility for the fused MFMA update path
-        (mfma_gemm.hip forward/dgrad/dW + ppo_loss.hip gh)."""
+        """Eligibility for the fused MFMA update path (mfma_gemm.hip
+        forward/dgrad/dW + the family's gh kernel: ppo_loss.hip for Box,
+        disc_gh.hip for Discrete, MultiDiscrete and MultiBinary).
+
+        The three discrete families need a head within the gh kernels'
+        limits (2 <= K <= 64; 1..32 components of >= 2 classes with
+        sum(nvec) <= 64; n <= 64) and at least P = 2 logit columns: the
+        combined-heads dW adds the (zero) gradient rows of gh's pad columns
+        to the flat gradient behind the value head's row, and only from
+        P = 2 on do all of them land inside the buffer.  P = 64
+        (ldgh = 68) is taken: the dgrad GEMM and the dW kernel guard rows
+        and columns by their runtime sizes.  DPPO_UPDATE_DISC=0 keeps these
+        families on the autograd update."""
         from .ops import use_hip
 
         c = self.cfg
-        if self._act_kind != "box" or c.DTYPE != "float32":
+        if c.DTYPE != "float32":
+            return False
+        if self._act_kind != "box" and not self._use_update_disc():
             return False
         if not use_hip(self.device, c.USE_HIP_KERNELS):
             return False
         if not (1 <= len(c.HIDDEN_SIZES) <= 3) or max(c.HIDDEN_SIZES) > 128:
             return False
-        if self.act_space.shape[0] > 32:
+        if self._act_kind == "box":
+            if self.act_space.shape[0] > 32:
+                return False
+        elif self._act_kind == "discrete":
+            if not (2 <= self.act_space.n <= 64):
+                return False
+        elif self._act_kind == "multidiscrete":
+            nvec = self._nvec
+            if not (1 <= len(nvec) <= 32 and min(nvec) >= 2
+                    and sum(nvec) <= 64):
+                return False
+        elif not (2 <= self.act_space.n <= 64):
             return False
         dims = [self.obs_space.shape[0], *c.HIDDEN_SIZES]
-        P, HL = 2 * self.act_space.shape[0], dims[-1]
+        P, HL = self.pi.pdtype.param_shape()[0], dims[-1]
         hsz = sum(dims[l + 1] * dims[l] for l in range(1, len(dims) - 1))
         return hsz + P * HL + HL <= 24576  # bwd staged-weight LDS budget
+
+    @staticmethod
+    def _use_update_disc() -> bool:
+        """DPPO_UPDATE_DISC: '0' keeps Discrete, MultiDiscrete and
+        MultiBinary policies on the autograd update loop, any other value
+        takes the fused MFMA update wherever _can_fuse_update() holds;
+        unset = the measured default below."""
+        ov = os.environ.get("DPPO_UPDATE_DISC")
+        if ov is not None:
+            return ov != "0"
+        # measured, T=64, ms per update() of 4 steps (tools/update_disc_ab.py,
+        # profiles/r11_update_disc.txt): CartPole (16,) autograd 2.02 / 5.97 /
+        # 56.5 vs fused 0.31 / 0.74 / 6.22 at E = 128 / 4096 / 65536;
+        # LunarLander (64,64) 2.42 / 10.9 / 97.6 vs 0.57 / 1.57 / 15.8;
+        # MultiLever (32,) 1.89 / 7.08 / 65.9 vs 0.33 / 0.81 / 7.45; BitFlipper
+        # (64,64) 2.39 / 9.72 / 81.5 vs 0.58 / 1.62 / 16.4.  Fused wins every
+        # alternated pair (4.1x at the least; spreads < 10 % autograd, < 0.3 %
+        # fused).  No crossover in the measured range -> on wherever eligible.
+        return True
 
     def update(self, batch: RolloutBatch, l_mul: float) -> None:
         """UPDATE_STEPS repeated full-batch steps on the same data
@@ -1358,7 +1401,7 @@ class DPPOEngine:
             # Graph capture of the RCCL all-reduce is unexercised on this
             # pool's multi-GPU boxes; keep multi-rank runs on the plain
             # fused path unless explicitly opted in (DPPO_GRAPH_DIST=1).
-            graph_ok = self.cfg.USE_GRAPHS and self._can_fuse_rollout() and (
+            graph_ok = self.cfg.USE_GRAPHS and self._batch_is_persistent() and (
                 not self.comm.distributed
                 or os.environ.get("DPPO_GRAPH_DIST") == "1"
             )
@@ -1373,6 +1416,14 @@ class DPPOEngine:
             losses["total_loss"].backward()
             self.comm.allreduce_mean_(self.flat_pi.flat_grad)
             self.optimizer.step()
+
+    def _batch_is_persistent(self) -> bool:
+        """The batch tensors are views of the persistent rollout / GAE
+        buffers, as a captured update needs: what every single-launch HIP
+        rollout (_rollout_once_fused, all four families) and the v3 rollout
+        guarantee, and the eager rollout loop does not."""
+        return (self._can_fuse_rollout() or self._use_rollout_cat()
+                or self._use_rollout_multi())
 
     def _update_minibatched(self, batch: RolloutBatch, l_mul: float) -> None:
         """Minibatched update steps (BASELINE config 4): each of the
@@ -1693,7 +1744,7 @@ class DPPOEngine:
         acts = torch.empty(B * sum(c.HIDDEN_SIZES), device=states.device,
                            dtype=states.dtype)
         a_views = self._acts_views(acts, B)
-        P = 2 * self.act_space.shape[0]
+        P = self.pi.pdtype.param_shape()[0]
         pdflat = torch.empty(B, P, device=states.device, dtype=states.dtype)
         v = torch.empty(B, device=states.device, dtype=states.dtype)
         if mw["heads_pad"] and self._fwd_fused():
@@ -1792,13 +1843,22 @@ class DPPOEngine:
         offsets = [sl.start for sl in self.flat_pi.slices]
         n_hidden = len(c.HIDDEN_SIZES)
         dgrad_code = 3 if c.ACTIVATION == "tanh" else 4
-        P = 2 * self.act_space.shape[0]
+        P = self.pi.pdtype.param_shape()[0]
         off_wv, off_bv = offsets[2 * n_hidden], offsets[2 * n_hidden + 1]
         off_wp, off_bp = offsets[2 * n_hidden + 2], offsets[2 * n_hidden + 3]
         dummy_bias = torch.zeros(1, device=self.device)
 
-        gh = ext.ppo_loss_gauss_gh(
-            pdflat, oldflat, v, oldv, actions, adv, etr,
+        # the family's loss-gradient kernel; all write the same
+        # [B][ldgh] operand (ops.ppo_loss.ppo_gh_ref)
+        gh_fn = {
+            "box": ext.ppo_loss_gauss_gh,
+            "discrete": ext.ppo_loss_cat_gh,
+            "multidiscrete": ext.ppo_loss_mcat_gh,
+            "multibinary": ext.ppo_loss_bern_gh,
+        }[self._act_kind]
+        nvec = (self._nvec,) if self._act_kind == "multidiscrete" else ()
+        gh = gh_fn(
+            pdflat, oldflat, v, oldv, actions, adv, etr, *nvec,
             clip, c.ENTCOEFF, c.VCOEFF, self._clip_dev_or_empty(),
         )
         # the staged PADDED [Wp; Wv; 0...]: its rows are the dgrad Wt
