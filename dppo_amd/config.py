@@ -61,6 +61,11 @@ REFERENCE_DEFAULTS: Dict[str, Any] = {
 }
 
 
+#: games with real dynamics (envs/classic.py), selected by
+#: ENV_DYNAMICS='physics'; every other GAME is a synthetic shape preset only
+PHYSICS_GAMES: Tuple[str, ...] = ("CartPole-v0", "Pendulum-v1")
+
+
 @dataclass
 class DPPOConfig:
     # ---- reference keys (main.py:12-29), same names/defaults ----
@@ -113,6 +118,10 @@ class DPPOConfig:
                                       # train on a BETTER rank's data; off =
                                       # rank-local batches (documented
                                       # deviation, PARITY.md §7)
+    ENV_DYNAMICS: str = "synthetic"   # 'synthetic': GAME is a shape preset
+                                      # over the synthetic env; 'physics':
+                                      # the game's real closed-form dynamics
+                                      # (envs/classic.py; PHYSICS_GAMES only)
 
     def __post_init__(self) -> None:
         if isinstance(self.HIDDEN_SIZES, list):
@@ -123,6 +132,14 @@ class DPPOConfig:
             raise ValueError(f"ACTIVATION must be 'relu' or 'tanh', got {self.ACTIVATION!r}")
         if self.USE_HIP_KERNELS not in ("auto", "always", "never"):
             raise ValueError("USE_HIP_KERNELS must be 'auto'|'always'|'never'")
+        if self.ENV_DYNAMICS not in ("synthetic", "physics"):
+            raise ValueError(
+                "ENV_DYNAMICS must be 'synthetic' or 'physics', got "
+                f"{self.ENV_DYNAMICS!r}")
+        if self.ENV_DYNAMICS == "physics" and self.GAME not in PHYSICS_GAMES:
+            raise ValueError(
+                f"GAME {self.GAME!r} has no physics; ENV_DYNAMICS='physics' "
+                f"supports {list(PHYSICS_GAMES)}")
 
     # -- construction --------------------------------------------------
     @classmethod

@@ -1,3 +1,5 @@
+from .classic import BatchedCartPole, BatchedPendulum
 from .synthetic import BatchedSyntheticEnv, make_env
 
-__all__ = ["BatchedSyntheticEnv", "make_env"]
+__all__ = ["BatchedCartPole", "BatchedPendulum", "BatchedSyntheticEnv",
+           "make_env"]

@@ -1,0 +1,159 @@
+"""Batched classic-control environments with real dynamics, resident on the
+training device.
+
+The reference steps gym's CartPole-v0 (reference main.py:13, Worker.py:10).
+CartPole and Pendulum are a dozen closed-form lines each, so they need no
+simulator: E envs per rank live as device tensors and step with batched torch
+ops (capture-safe, no host sync; this is also the CPU path) or inside the
+lane-per-env HIP rollout (ops/hip/classic_rollout.hip), whose device math in
+ops/hip/classic_env.h reproduces the float32 expressions below.
+
+CartPole-v0: state = observation = (x, x_dot, theta, theta_dot), Discrete(2),
+reward 1 per step, terminates when |x| > 2.4 or |theta| > 12 degrees.
+Pendulum-v1: state (theta, theta_dot), observation (cos, sin, theta_dot),
+Box(-1, 1, (1,)) scaled to a torque in [-2, 2], never terminates.
+Both truncate at `time_limit` steps.  As everywhere in this project the
+observation returned on a done step is the fresh one and the reward belongs
+to the pre-reset transition.
+"""
+
+from __future__ import annotations
+
+import math
+
+import torch
+
+from .. import spaces
+from ..config import DPPOConfig, game_spaces
+
+CARTPOLE, PENDULUM = 0, 1       # env ids of the HIP rollout bindings
+
+X_LIMIT = 2.4
+THETA_LIMIT = 0.20943951        # 12 degrees
+TWO_PI = 2.0 * math.pi
+
+
+def cartpole_step(s: torch.Tensor, a: torch.Tensor):
+    """One Euler step of CartPole from states s [N, 4] under actions a [N]
+    (1 pushes right, anything else left): (s' [N, 4], reward [N],
+    terminated [N] bool)."""
+    x, xd, th, thd = s.unbind(-1)
+    force = torch.where(a.reshape(-1) == 1, 10.0, -10.0).to(s.dtype)
+    sin, cos = torch.sin(th), torch.cos(th)
+    temp = (force + 0.05 * thd * thd * sin) / 1.1
+    thacc = (9.8 * sin - cos * temp) / (
+        0.5 * (4.0 / 3.0 - 0.1 * cos * cos / 1.1))
+    xacc = temp - 0.05 * thacc * cos / 1.1
+    tau = 0.02
+    s2 = torch.stack(
+        [x + tau * xd, xd + tau * xacc, th + tau * thd, thd + tau * thacc],
+        dim=-1)
+    term = (s2[..., 0].abs() > X_LIMIT) | (s2[..., 2].abs() > THETA_LIMIT)
+    return s2, torch.ones_like(x), term
+
+
+def pendulum_step(s: torch.Tensor, a: torch.Tensor):
+    """One step of Pendulum from states s [N, 2] = (theta, theta_dot) under
+    actions a [N] or [N, 1]: (s' [N, 2], reward [N], terminated [N] bool,
+    never set).  The action is clipped to [-1, 1] here, inside the physics,
+    and theta' is wrapped into [-pi, pi)."""
+    th, thd = s.unbind(-1)
+    u = 2.0 * a.reshape(-1).to(s.dtype).clamp(-1.0, 1.0)
+    reward = -(th * th + 0.1 * thd * thd + 0.001 * u * u)
+    thd2 = (thd + (15.0 * torch.sin(th) + 3.0 * u) * 0.05).clamp(-8.0, 8.0)
+    z = th + 0.05 * thd2
+    th2 = z - TWO_PI * torch.floor((z + math.pi) / TWO_PI)
+    return (torch.stack([th2, thd2], dim=-1), reward,
+            torch.zeros_like(th, dtype=torch.bool))
+
+
+def pendulum_obs(s: torch.Tensor) -> torch.Tensor:
+    th, thd = s.unbind(-1)
+    return torch.stack([torch.cos(th), torch.sin(th), thd], dim=-1)
+
+
+class BatchedClassicEnv:
+    """E parallel physics envs on one device, with BatchedSyntheticEnv's
+    vectorised API: reset() -> obs [E, obs_dim]; step(actions) -> (obs,
+    reward [E], done [E], info) with auto-reset.  `s` [E, S] is the internal
+    state, `x` the current observation, `t` the per-env step counter."""
+
+    ENV_ID: int
+    GAME: str
+    S: int                      # state width
+    #: reset range per state dim: s_d uniform in (-RESET_HALF[d], RESET_HALF[d]]
+    RESET_HALF: tuple
+
+    def __init__(self, num_envs: int, device: str = "cpu", seed: int = 0,
+                 time_limit: int = 200):
+        self.observation_space, self.action_space = game_spaces(self.GAME)
+        self.num_envs = num_envs
+        self.device = torch.device(device)
+        self.time_limit = int(time_limit)
+        self.dtype = torch.float32
+        self.obs_dim = self.observation_space.shape[0]
+        self._gen = torch.Generator(device=self.device.type).manual_seed(seed)
+        self._half = torch.tensor(self.RESET_HALF, device=self.device)
+        self.horizons_i32 = torch.full(
+            (num_envs,), self.time_limit, device=self.device,
+            dtype=torch.int32)
+        self.s = torch.zeros(num_envs, self.S, device=self.device)
+        self.x = self._obs(self.s)
+        self.t = torch.zeros(num_envs, device=self.device, dtype=torch.int32)
+
+    # -- per-game pieces -------------------------------------------------
+    def _physics(self, s, a):
+        raise NotImplementedError
+
+    def _obs(self, s: torch.Tensor) -> torch.Tensor:
+        return s.clone()
+
+    # --------------------------------------------------------------------
+    def seed_state(self) -> torch.Tensor:
+        # u in (0, 1], as the HIP rollout's rng_uniform
+        u = 1.0 - torch.rand(self.num_envs, self.S, generator=self._gen,
+                             device=self.device)
+        return (2.0 * u - 1.0) * self._half
+
+    def reset(self) -> torch.Tensor:
+        self.s = self.seed_state()
+        self.x = self._obs(self.s)
+        self.t.zero_()
+        return self.x
+
+    def step(self, actions: torch.Tensor):
+        s2, reward, term = self._physics(self.s, actions)
+        t2 = self.t + 1
+        done = term | (t2 >= self.time_limit)
+        # auto-reset (capture-safe): done envs restart from a fresh state
+        self.s = torch.where(done.unsqueeze(-1), self.seed_state(), s2)
+        self.x = self._obs(self.s)
+        self.t = torch.where(done, torch.zeros_like(t2), t2)
+        return self.x, reward, done, {}
+
+
+class BatchedCartPole(BatchedClassicEnv):
+    ENV_ID, GAME, S = CARTPOLE, "CartPole-v0", 4
+    RESET_HALF = (0.05, 0.05, 0.05, 0.05)
+
+    def _physics(self, s, a):
+        return cartpole_step(s, a)
+
+
+class BatchedPendulum(BatchedClassicEnv):
+    ENV_ID, GAME, S = PENDULUM, "Pendulum-v1", 2
+    RESET_HALF = (math.pi, 1.0)
+
+    def _physics(self, s, a):
+        return pendulum_step(s, a)
+
+    def _obs(self, s):
+        return pendulum_obs(s)
+
+
+CLASSIC_ENVS = {cls.GAME: cls for cls in (BatchedCartPole, BatchedPendulum)}
+
+
+def make_classic_env(cfg: DPPOConfig, device: str,
+                     seed: int) -> BatchedClassicEnv:
+    return CLASSIC_ENVS[cfg.GAME](cfg.NUM_ENVS, device=device, seed=seed)

@@ -159,7 +159,13 @@ class BatchedSyntheticEnv:
         return self.x, reward.to(self.dtype), done, {}
 
 
-def make_env(cfg: DPPOConfig, device: str, seed: int) -> BatchedSyntheticEnv:
+def make_env(cfg: DPPOConfig, device: str, seed: int):
+    """The env of cfg: the game's real dynamics (envs/classic.py) for
+    ENV_DYNAMICS='physics', else the synthetic env of the game's shapes."""
+    if cfg.ENV_DYNAMICS == "physics":
+        from .classic import make_classic_env
+
+        return make_classic_env(cfg, device, seed)
     obs_space, act_space = game_spaces(cfg.GAME)
     return BatchedSyntheticEnv(
         obs_space,

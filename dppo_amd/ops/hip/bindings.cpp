@@ -228,7 +228,28 @@ torch::Tensor ppo_loss_bern_gh(torch::Tensor lpi, torch::Tensor lold,
 
 int64_t ppo_gh_disc_tile(int64_t P, int64_t act_width);
 
+std::vector<torch::Tensor> classic_rollout_cat(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation, int64_t env_id,
+    torch::Tensor s, int64_t time_limit, double eps_explore, torch::Tensor x,
+    torch::Tensor t, torch::Tensor epr, int64_t T, int64_t n_actions,
+    int64_t seed, torch::Tensor out_buf);
+
+std::vector<torch::Tensor> classic_rollout_box(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation, int64_t env_id,
+    torch::Tensor s, int64_t time_limit, double act_low, double act_high,
+    double eps_explore, torch::Tensor x, torch::Tensor t, torch::Tensor epr,
+    int64_t T, int64_t act_dim, int64_t seed, torch::Tensor out_buf);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("classic_rollout_cat", &classic_rollout_cat,
+          "lane-per-env T-step CartPole rollout, Discrete(2)/Categorical "
+          "policy: MLP fwd + Gumbel-max sample + physics step, int64 actions; "
+          "rollout_run_cat's out blob (gfx950)");
+  mod.def("classic_rollout_box", &classic_rollout_box,
+          "lane-per-env T-step Pendulum rollout, Box(1)/DiagGaussian policy: "
+          "MLP fwd + sample + physics step; rollout_run's out blob (gfx950)");
   mod.def("ppo_loss_cat_gh", &ppo_loss_cat_gh,
           "Categorical PPO loss gradient -> gh [B][ldgh] = [g_logits | g_v | "
           "0], int64 actions [B]; layout: ops.ppo_loss.ppo_gh_ref (gfx950)");

@@ -127,6 +127,9 @@ class DPPOEngine:
         self._fwd_fused_cache = self._mid_mode_cache = None
         self.fwd_fused_launches = {}    # mlp_fwd_fused launches per use
         self.env_rows_launches = 0      # env_step_rows launches
+        self.classic_rollout_launches = 0  # classic_rollout_* launches
+        # real dynamics (envs/classic.py) instead of the synthetic env
+        self._physics = cfg.ENV_DYNAMICS == "physics"
         self._clip_dev = None           # device clip for captured updates
         self._upd_graph = self._upd_graph_skip = None
         self._graph_failed = False
@@ -367,7 +370,7 @@ class DPPOEngine:
         """Eligibility for the fused HIP rollout kernel (rollout.hip):
         Box/DiagGaussian policy, dims within kernel limits, fp32, GPU."""
         c = self.cfg
-        if not self._hip_path("box"):
+        if self._physics or not self._hip_path("box"):
             return False
         if not (1 <= len(c.HIDDEN_SIZES) <= 3):
             return False
@@ -379,6 +382,8 @@ class DPPOEngine:
 
     @torch.no_grad()
     def rollout_once(self) -> Tuple[RolloutBatch, Dict[str, float]]:
+        if self._use_rollout_classic():
+            return self._rollout_once_hip_classic()
         if self._can_rollout_v3():
             return self._rollout_once_hip_v3()
         if self._can_fuse_rollout():
@@ -396,7 +401,7 @@ class DPPOEngine:
         _can_fuse_rollout(), which also gates the Box-only v3 rollout and
         graphed update."""
         c = self.cfg
-        if not self._hip_path("discrete"):
+        if self._physics or not self._hip_path("discrete"):
             return False
         if not (1 <= len(c.HIDDEN_SIZES) <= 3):
             return False
@@ -435,8 +440,8 @@ class DPPOEngine:
         limits, fp32, GPU.  Its own function: _can_fuse_rollout_cat() stays
         False for these games."""
         c = self.cfg
-        if not (self._hip_path("multidiscrete")
-                or self._hip_path("multibinary")):
+        if self._physics or not (self._hip_path("multidiscrete")
+                                 or self._hip_path("multibinary")):
             return False
         if not (1 <= len(c.HIDDEN_SIZES) <= 3):
             return False
@@ -484,6 +489,81 @@ class DPPOEngine:
         # measured crossover: fused 6.8 vs v3 9.1 ms at E=16384, fused
         # 13.0 vs v3 10.3 ms at E=32768 (tools/rollout_v3_ab.py)
         return self.cfg.NUM_ENVS >= 32768
+
+    def _can_rollout_classic(self) -> bool:
+        """Eligibility for the lane-per-env physics rollout
+        (ops/hip/classic_rollout.hip): a physics env, fp32, GPU, and the
+        kernel's trunk limits (1-2 hidden layers of width <= 64, which the
+        bindings check too)."""
+        H = self.cfg.HIDDEN_SIZES
+        return (self._physics and self._hip_path(self._act_kind)
+                and 1 <= len(H) <= 2 and max(H) <= 64)
+
+    def _use_rollout_classic(self) -> bool:
+        """Dispatch for physics envs: DPPO_ROLLOUT_CLASSIC=0 forces the
+        eager loop, any other value the kernel wherever eligible."""
+        if not self._can_rollout_classic():
+            return False
+        ov = os.environ.get("DPPO_ROLLOUT_CLASSIC")
+        if ov is not None:
+            return ov != "0"
+        # measured, T=64, ms per rollout_once() (tools/rollout_classic_ab.py,
+        # profiles/r12_rollout_classic.txt): CartPole (16,) eager 34.7 / 35.0 /
+        # 34.6 vs kernel 0.22 / 0.23 / 0.31 at E = 128 / 4096 / 65536;
+        # CartPole (64,64) 36.9 / 37.9 / 40.2 vs 1.32 / 1.34 / 1.97; Pendulum
+        # (16,) 36.1 / 33.2 / 32.9 vs 0.20 / 0.21 / 0.28.  The kernel wins
+        # every alternated pair (20x at the least; widest min..max spread
+        # 3.9 ms eager, 0.004 ms kernel).  No crossover in the measured
+        # range -> on wherever eligible.  (Measured with the moments still
+        # taken by ep_moments_kernel after the rollout; the in-kernel fold
+        # that replaced it drops two launches and is not re-measured.)
+        # classic_rollout_kernel<FAM, ENV, NH> for gfx950 (FAM 0 Box / 1
+        # Categorical, ENV 0 CartPole / 1 Pendulum, NH hidden layers), no
+        # VGPR spills, scratch 0 in all four (<1,0,2> keeps 8 SGPRs in VGPR
+        # lanes):
+        #   <1,0,1> VGPR  65 SGPR  91 LDS   592 B at (16,)    occ 7
+        #   <1,0,2> VGPR 115 SGPR 106 LDS 35344 B at (64,64)  occ 4 (LDS: 1)
+        #   <0,1,1> VGPR  65 SGPR  81 LDS   528 B at (16,)    occ 7
+        #   <0,1,2> VGPR 120 SGPR 100 LDS 35088 B at (64,64)  occ 4 (LDS: 1)
+        return True
+
+    @torch.no_grad()
+    def _rollout_once_hip_classic(self) -> Tuple[RolloutBatch, Dict[str, float]]:
+        """Physics rollout in a single launch, one lane per env
+        (classic_rollout.hip): policy forward + sampling + epsilon overlay +
+        CartPole / Pendulum step + episode bookkeeping and resets for all T
+        steps, into the out blob layouts of rollout_run_cat / rollout_run."""
+        from .ops import hip_ext
+
+        ext = hip_ext()
+        c, E, T = self.cfg, self.cfg.NUM_ENVS, self.cfg.MAX_EPOCH_STEPS
+        eps = self.exploration_rate()
+        env = self.env
+        seed = self._next_rollout_seed()
+        blob, offsets, dims = self._rollout_weight_blob()
+        D = self.obs_space.shape[0]
+        if self._discrete:
+            n_act = self.act_space.n
+            n_out = T * E * (2 + D + n_act + 3) + E + 5
+            run, bounds = ext.classic_rollout_cat, ()
+        else:
+            n_act = self.act_space.shape[0]
+            n_out = T * E * (D + 3 * n_act + 3) + E + 5
+            run, bounds = ext.classic_rollout_box, self._act_bounds()
+        out = self._rollout_outputs(n_out)
+        self._v3_acts_valid = False  # no recorded activations
+        self._wide_rollout_h_valid = False
+        (states, pdflats, actions, values, rewards, dones, boot_v,
+         moments) = run(
+            blob, offsets, dims, self._act_code,
+            env.ENV_ID, env.s, env.time_limit, *bounds, float(eps),
+            env.x, env.t, self.epr, T, n_act, seed, out,
+        )
+        self.classic_rollout_launches += 1
+        self.obs = env.x  # updated in place by the kernel
+        return self._finish_hip_rollout(
+            states, pdflats, actions, values, rewards, dones, boot_v,
+            moments, eps)
 
     @torch.no_grad()
     def _rollout_weight_blob(self):
@@ -1420,10 +1500,11 @@ class DPPOEngine:
     def _batch_is_persistent(self) -> bool:
         """The batch tensors are views of the persistent rollout / GAE
         buffers, as a captured update needs: what every single-launch HIP
-        rollout (_rollout_once_fused, all four families) and the v3 rollout
-        guarantee, and the eager rollout loop does not."""
+        rollout (_rollout_once_fused, all four families, and the physics
+        rollout) and the v3 rollout guarantee, and the eager rollout loop
+        does not."""
         return (self._can_fuse_rollout() or self._use_rollout_cat()
-                or self._use_rollout_multi())
+                or self._use_rollout_multi() or self._use_rollout_classic())
 
     def _update_minibatched(self, batch: RolloutBatch, l_mul: float) -> None:
         """Minibatched update steps (BASELINE config 4): each of the
