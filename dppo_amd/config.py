@@ -63,7 +63,7 @@ REFERENCE_DEFAULTS: Dict[str, Any] = {
 
 #: games with real dynamics (envs/classic.py), selected by
 #: ENV_DYNAMICS='physics'; every other GAME is a synthetic shape preset only
-PHYSICS_GAMES: Tuple[str, ...] = ("CartPole-v0", "Pendulum-v1")
+PHYSICS_GAMES: Tuple[str, ...] = ("CartPole-v0", "Pendulum-v1", "Acrobot-v1")
 
 
 @dataclass

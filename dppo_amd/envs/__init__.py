@@ -1,5 +1,5 @@
-from .classic import BatchedCartPole, BatchedPendulum
+from .classic import BatchedAcrobot, BatchedCartPole, BatchedPendulum
 from .synthetic import BatchedSyntheticEnv, make_env
 
-__all__ = ["BatchedCartPole", "BatchedPendulum", "BatchedSyntheticEnv",
-           "make_env"]
+__all__ = ["BatchedAcrobot", "BatchedCartPole", "BatchedPendulum",
+           "BatchedSyntheticEnv", "make_env"]

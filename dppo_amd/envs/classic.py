@@ -2,8 +2,8 @@
 training device.
 
 The reference steps gym's CartPole-v0 (reference main.py:13, Worker.py:10).
-CartPole and Pendulum are a dozen closed-form lines each, so they need no
-simulator: E envs per rank live as device tensors and step with batched torch
+CartPole, Pendulum and Acrobot are a dozen closed-form lines each, so they
+need no simulator: E envs per rank live as device tensors and step with batched torch
 ops (capture-safe, no host sync; this is also the CPU path) or inside the
 lane-per-env HIP rollout (ops/hip/classic_rollout.hip), whose device math in
 ops/hip/classic_env.h reproduces the float32 expressions below.
@@ -12,7 +12,12 @@ CartPole-v0: state = observation = (x, x_dot, theta, theta_dot), Discrete(2),
 reward 1 per step, terminates when |x| > 2.4 or |theta| > 12 degrees.
 Pendulum-v1: state (theta, theta_dot), observation (cos, sin, theta_dot),
 Box(-1, 1, (1,)) scaled to a torque in [-2, 2], never terminates.
-Both truncate at `time_limit` steps.  As everywhere in this project the
+Acrobot-v1: state (theta1, theta2, omega1, omega2), observation (cos theta1,
+sin theta1, cos theta2, sin theta2, omega1, omega2), Discrete(3) giving a
+torque of -1 / 0 / +1 on the second joint, one RK4 step of gym's "book"
+dynamics per env step, reward -1 per step until the tip clears the bar
+(-cos theta1 - cos(theta1 + theta2) > 1), which terminates with reward 0.
+All truncate at `time_limit` steps (200, 200 and 500 by default).  As everywhere in this project the
 observation returned on a done step is the fresh one and the reward belongs
 to the pre-reset transition.
 """
@@ -27,6 +32,7 @@ from .. import spaces
 from ..config import DPPOConfig, game_spaces
 
 CARTPOLE, PENDULUM = 0, 1       # env ids of the HIP rollout bindings
+ACROBOT = 2
 
 X_LIMIT = 2.4
 THETA_LIMIT = 0.20943951        # 12 degrees
@@ -72,6 +78,66 @@ def pendulum_obs(s: torch.Tensor) -> torch.Tensor:
     return torch.stack([torch.cos(th), torch.sin(th), thd], dim=-1)
 
 
+ACROBOT_DT = 0.2
+ACROBOT_MAX_VEL_1 = 4.0 * math.pi
+ACROBOT_MAX_VEL_2 = 9.0 * math.pi
+
+
+def _acrobot_deriv(th1, th2, w1, w2, tau):
+    """(alpha1, alpha2) of gym's "book" Acrobot with every link constant 1,
+    lc = 0.5, I = 1, g = 9.8, the constants folded and cos(x - pi/2) written
+    as sin x."""
+    s1, s2, c2 = torch.sin(th1), torch.sin(th2), torch.cos(th2)
+    d1 = 3.5 + c2
+    d2 = 1.25 + 0.5 * c2
+    phi2 = 4.9 * torch.sin(th1 + th2)
+    phi1 = -0.5 * w2 * w2 * s2 - w2 * w1 * s2 + 14.7 * s1 + phi2
+    a2 = (tau + d2 / d1 * phi1 - 0.5 * w1 * w1 * s2 - phi2) / (
+        1.25 - d2 * d2 / d1)
+    a1 = -(d2 * a2 + phi1) / d1
+    return a1, a2
+
+
+def acrobot_step(s: torch.Tensor, a: torch.Tensor):
+    """One classical RK4 step (dt = 0.2, torque a - 1 held constant) of
+    Acrobot from states s [N, 4] = (theta1, theta2, omega1, omega2) under
+    actions a [N] in {0, 1, 2}: (s' [N, 4], reward [N], terminated [N] bool).
+    The angles of s' are wrapped into [-pi, pi), omega1' is clamped to
+    +-4 pi and omega2' to +-9 pi; the reward is -1, or 0 on a terminating
+    step.  The weighted sum k1 + 2 k2 + 2 k3 + k4 is accumulated stage by
+    stage, in this order, as the kernel does."""
+    y = s.unbind(-1)
+    tau = a.reshape(-1).to(s.dtype) - 1.0
+    h = ACROBOT_DT
+
+    def f(th1, th2, w1, w2):
+        a1, a2 = _acrobot_deriv(th1, th2, w1, w2, tau)
+        return (w1, w2, a1, a2)
+
+    k = f(*y)                                               # k1
+    acc = k
+    k = f(*(yi + (0.5 * h) * ki for yi, ki in zip(y, k)))   # k2
+    acc = tuple(ai + 2.0 * ki for ai, ki in zip(acc, k))
+    k = f(*(yi + (0.5 * h) * ki for yi, ki in zip(y, k)))   # k3
+    acc = tuple(ai + 2.0 * ki for ai, ki in zip(acc, k))
+    k = f(*(yi + h * ki for yi, ki in zip(y, k)))           # k4
+    acc = tuple(ai + ki for ai, ki in zip(acc, k))
+    z1, z2, w1, w2 = (yi + (h / 6.0) * ai for yi, ai in zip(y, acc))
+    th1 = z1 - TWO_PI * torch.floor((z1 + math.pi) / TWO_PI)
+    th2 = z2 - TWO_PI * torch.floor((z2 + math.pi) / TWO_PI)
+    w1 = w1.clamp(-ACROBOT_MAX_VEL_1, ACROBOT_MAX_VEL_1)
+    w2 = w2.clamp(-ACROBOT_MAX_VEL_2, ACROBOT_MAX_VEL_2)
+    term = -torch.cos(th1) - torch.cos(th1 + th2) > 1.0
+    reward = torch.where(term, 0.0, -1.0).to(s.dtype)
+    return torch.stack([th1, th2, w1, w2], dim=-1), reward, term
+
+
+def acrobot_obs(s: torch.Tensor) -> torch.Tensor:
+    th1, th2, w1, w2 = s.unbind(-1)
+    return torch.stack([torch.cos(th1), torch.sin(th1), torch.cos(th2),
+                        torch.sin(th2), w1, w2], dim=-1)
+
+
 class BatchedClassicEnv:
     """E parallel physics envs on one device, with BatchedSyntheticEnv's
     vectorised API: reset() -> obs [E, obs_dim]; step(actions) -> (obs,
@@ -83,9 +149,11 @@ class BatchedClassicEnv:
     S: int                      # state width
     #: reset range per state dim: s_d uniform in (-RESET_HALF[d], RESET_HALF[d]]
     RESET_HALF: tuple
+    #: the game's registered episode length, the default `time_limit`
+    TIME_LIMIT = 200
 
     def __init__(self, num_envs: int, device: str = "cpu", seed: int = 0,
-                 time_limit: int = 200):
+                 time_limit: int = TIME_LIMIT):
         self.observation_space, self.action_space = game_spaces(self.GAME)
         self.num_envs = num_envs
         self.device = torch.device(device)
@@ -151,7 +219,25 @@ class BatchedPendulum(BatchedClassicEnv):
         return pendulum_obs(s)
 
 
-CLASSIC_ENVS = {cls.GAME: cls for cls in (BatchedCartPole, BatchedPendulum)}
+class BatchedAcrobot(BatchedClassicEnv):
+    ENV_ID, GAME, S = ACROBOT, "Acrobot-v1", 4
+    RESET_HALF = (0.1, 0.1, 0.1, 0.1)
+    TIME_LIMIT = 500
+
+    def __init__(self, num_envs: int, device: str = "cpu", seed: int = 0,
+                 time_limit: int = TIME_LIMIT):
+        super().__init__(num_envs, device=device, seed=seed,
+                         time_limit=time_limit)
+
+    def _physics(self, s, a):
+        return acrobot_step(s, a)
+
+    def _obs(self, s):
+        return acrobot_obs(s)
+
+
+CLASSIC_ENVS = {cls.GAME: cls for cls in (BatchedCartPole, BatchedPendulum,
+                                          BatchedAcrobot)}
 
 
 def make_classic_env(cfg: DPPOConfig, device: str,

@@ -244,9 +244,10 @@ std::vector<torch::Tensor> classic_rollout_box(
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("classic_rollout_cat", &classic_rollout_cat,
-          "lane-per-env T-step CartPole rollout, Discrete(2)/Categorical "
-          "policy: MLP fwd + Gumbel-max sample + physics step, int64 actions; "
-          "rollout_run_cat's out blob (gfx950)");
+          "lane-per-env T-step CartPole (env_id 0, Discrete(2)) or Acrobot "
+          "(env_id 2, Discrete(3), RK4) rollout, Categorical policy: MLP fwd + "
+          "Gumbel-max sample + physics step, int64 actions; rollout_run_cat's "
+          "out blob with K = n_actions (gfx950)");
   mod.def("classic_rollout_box", &classic_rollout_box,
           "lane-per-env T-step Pendulum rollout, Box(1)/DiagGaussian policy: "
           "MLP fwd + sample + physics step; rollout_run's out blob (gfx950)");

@@ -1,7 +1,7 @@
-// Classic-control device math: the CartPole-v0 and Pendulum-v1 transitions,
-// their reset draws and observations, as functions of scalars.  The float32
-// expressions are those of envs/classic.py (cartpole_step, pendulum_step),
-// which the tests hold the kernel to.  sinf / cosf / floorf are the accurate
+// Classic-control device math: the CartPole-v0, Pendulum-v1 and Acrobot-v1
+// transitions, their reset draws and observations, as functions of scalars.
+// The float32 expressions are those of envs/classic.py (cartpole_step,
+// pendulum_step, acrobot_step), which the tests hold the kernel to.  sinf / cosf / floorf are the accurate
 // forms on purpose: the state is integrated over hundreds of steps.
 // RNG, slot scheme and samplers are rollout_math.h's.
 #pragma once
@@ -10,8 +10,10 @@
 
 constexpr int ENV_CARTPOLE = 0;
 constexpr int ENV_PENDULUM = 1;
+constexpr int ENV_ACROBOT = 2;
 
-// per-env shapes: S state scalars, D observation scalars
+// per-env shapes: S state scalars, D observation scalars, P policy-head
+// columns (Categorical: the logits; DiagGaussian with A = 1: mean, logstd)
 template <int ENV>
 struct ClassicEnv;
 
@@ -19,12 +21,21 @@ template <>
 struct ClassicEnv<ENV_CARTPOLE> {
   static constexpr int S = 4;  // x, x_dot, theta, theta_dot
   static constexpr int D = 4;  // the state itself
+  static constexpr int P = 2;
 };
 
 template <>
 struct ClassicEnv<ENV_PENDULUM> {
   static constexpr int S = 2;  // theta, theta_dot
   static constexpr int D = 3;  // cos theta, sin theta, theta_dot
+  static constexpr int P = 2;
+};
+
+template <>
+struct ClassicEnv<ENV_ACROBOT> {
+  static constexpr int S = 4;  // theta1, theta2, omega1, omega2
+  static constexpr int D = 6;  // cos, sin of theta1; cos, sin of theta2; omegas
+  static constexpr int P = 3;
 };
 
 // One Euler step (tau = 0.02) under action a (1 pushes right, else left),
@@ -62,15 +73,79 @@ DEV_INLINE int pendulum_step(float* s, float a, float& reward) {
   return 0;
 }
 
+// wrap an angle into [-pi, pi) (the floor form of pendulum_step)
+DEV_INLINE float wrap_pi(float z) {
+  return z - 6.2831853071795865f *
+                 floorf((z + 3.1415926535897932f) / 6.2831853071795865f);
+}
+
+// Angular accelerations of gym's "book" Acrobot, every link constant 1,
+// lc = 0.5, I = 1, g = 9.8, constants folded and cos(x - pi/2) as sin x.
+// sin / cos of theta2 are recomputed per evaluation: nothing but the stage
+// state lives across the four RK4 stages.
+DEV_INLINE void acrobot_accel(float th1, float th2, float w1, float w2,
+                              float tau, float& a1, float& a2) {
+  float s2, c2;
+  sincosf(th2, &s2, &c2);
+  const float s1 = sinf(th1);
+  const float d1 = 3.5f + c2;
+  const float d2 = 1.25f + 0.5f * c2;
+  const float phi2 = 4.9f * sinf(th1 + th2);
+  const float phi1 = -0.5f * w2 * w2 * s2 - w2 * w1 * s2 + 14.7f * s1 + phi2;
+  a2 = (tau + d2 / d1 * phi1 - 0.5f * w1 * w1 * s2 - phi2) /
+       (1.25f - d2 * d2 / d1);
+  a1 = -(d2 * a2 + phi1) / d1;
+}
+
+// One classical RK4 step (dt = 0.2) under action a in {0, 1, 2}: torque
+// a - 1 on the second joint, held over the step.  Stage q evaluates f at
+// y + c_q k_{q-1} with c = (0, 0.1, 0.1, 0.2) and adds w_q k_q, w = (1, 2, 2,
+// 1), to the running sum, in that order (acrobot_step of envs/classic.py;
+// 0 + 1 k1, acc + 2 k and acc + 1 k4 round as k1, acc + 2 k and acc + k4 do,
+// fused or not).  The stage loop stays rolled: one copy of the four sine
+// expansions instead of four.  Angles are wrapped into [-pi, pi), omega1
+// clamped to +-4 pi, omega2 to +-9 pi.  Reward -1, or 0 on the terminating
+// step; returns the termination flag of the new state.
+DEV_INLINE int acrobot_step(float* s, int a, float& reward) {
+  const float tau = (float)a - 1.0f;
+  float k0 = 0.f, k1 = 0.f, k2 = 0.f, k3 = 0.f;
+  float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+#pragma unroll 1
+  for (int q = 0; q < 4; ++q) {
+    const float c = (q == 0) ? 0.0f : (q == 3) ? 0.2f : 0.1f;
+    const float w = (q == 0 || q == 3) ? 1.0f : 2.0f;
+    const float th1 = s[0] + c * k0, th2 = s[1] + c * k1;
+    const float w1 = s[2] + c * k2, w2 = s[3] + c * k3;
+    k0 = w1;
+    k1 = w2;
+    acrobot_accel(th1, th2, w1, w2, tau, k2, k3);
+    acc0 += w * k0;
+    acc1 += w * k1;
+    acc2 += w * k2;
+    acc3 += w * k3;
+  }
+  const float h6 = 0.2f / 6.0f;
+  s[0] = wrap_pi(s[0] + h6 * acc0);
+  s[1] = wrap_pi(s[1] + h6 * acc1);
+  s[2] = fminf(fmaxf(s[2] + h6 * acc2, -12.566370614359172f),
+               12.566370614359172f);
+  s[3] = fminf(fmaxf(s[3] + h6 * acc3, -28.274333882308138f),
+               28.274333882308138f);
+  const int term = (-cosf(s[0]) - cosf(s[0] + s[1]) > 1.0f) ? 1 : 0;
+  reward = term ? 0.0f : -1.0f;
+  return term;
+}
+
 // fresh state of a finished env: dim d uniform in (-half_d, half_d] from the
 // RNG_SLOT_RESET + d draw of (env, step)
 template <int ENV>
 DEV_INLINE void classic_reset(float* s, unsigned seed, int env, int step) {
 #pragma unroll
   for (int d = 0; d < ClassicEnv<ENV>::S; ++d) {
-    const float half = (ENV == ENV_CARTPOLE) ? 0.05f
-                       : (d == 0)            ? 3.1415926535897932f
-                                             : 1.0f;
+    const float half = (ENV == ENV_CARTPOLE)  ? 0.05f
+                       : (ENV == ENV_ACROBOT) ? 0.1f
+                       : (d == 0)             ? 3.1415926535897932f
+                                              : 1.0f;
     const float u = rng_uniform(seed, env, step, RNG_SLOT_RESET + d);
     s[d] = (2.0f * u - 1.0f) * half;
   }
@@ -82,6 +157,11 @@ DEV_INLINE void classic_obs(const float* s, float* x) {
   if constexpr (ENV == ENV_CARTPOLE) {
 #pragma unroll
     for (int d = 0; d < 4; ++d) x[d] = s[d];
+  } else if constexpr (ENV == ENV_ACROBOT) {
+    sincosf(s[0], &x[1], &x[0]);
+    sincosf(s[1], &x[3], &x[2]);
+    x[4] = s[2];
+    x[5] = s[3];
   } else {
     x[0] = cosf(s[0]);
     x[1] = sinf(s[0]);

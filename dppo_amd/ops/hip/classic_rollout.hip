@@ -1,5 +1,5 @@
-// Classic-control rollout (gfx950): the whole T-step rollout of CartPole-v0
-// or Pendulum-v1 in one launch, ONE LANE PER ENV.
+// Classic-control rollout (gfx950): the whole T-step rollout of CartPole-v0,
+// Pendulum-v1 or Acrobot-v1 in one launch, ONE LANE PER ENV.
 //
 // A classic-control env is a handful of scalars, so rollout.hip's
 // decomposition (8 envs per 256-thread block, lanes split over the
@@ -27,16 +27,25 @@
 //     reads one image dword + four weight float4s per 16 FMAs (units 16 at
 //     a time, a 4-unit tile for the rest).
 //   - The LAST hidden layer is never stored: each unit is folded into the
-//     three head accumulators (v, p0, p1) as it is produced.  Both envs have
-//     P = 2 head columns (CartPole: 2 logits; Pendulum: mean, logstd), and
-//     heads are staged as one float4 (Wv, Wp0, Wp1, 0) per unit.
+//     1 + P head accumulators (v, p0, p1 and, for P = 3, p2) as it is
+//     produced.  P, the number of policy-head columns, is a compile-time
+//     property of the env (ClassicEnv<ENV>::P): 2 for CartPole (2 logits) and
+//     Pendulum (mean, logstd), 3 for Acrobot (3 logits).  Heads are staged as
+//     one float4 (Wv, Wp0, Wp1, Wp2 or 0) per unit, so P = 3 fills the lane
+//     that P = 2 pads and the LDS layout is the same for both.
+//   - The env step runs in scalar registers.  Acrobot's is one RK4 step: four
+//     derivative evaluations with their own sines and cosines
+//     (classic_env.h), about the cost of a (16,) trunk.
 // Per-step global writes have lane == env ([T][E] and [T][E][D] rows), so
 // they are coalesced by construction; 16-byte CartPole state rows and 8-byte
-// pd rows go out as one vector store where the row base is aligned.
+// pd rows go out as one vector store, 24-byte Acrobot state rows as three
+// float2 stores, where the row base is aligned; 12-byte K = 3 pd rows go out
+// as scalars (lane stride 12 B is still a dense wave write).
 //
 // Limits (checked in the bindings, mirrored by the engine's
 // _can_rollout_classic): 1-2 hidden layers of width <= 64; Categorical with
-// K = 2 on CartPole, DiagGaussian with A = 1 on Pendulum.
+// K = 2 on CartPole and K = 3 on Acrobot, DiagGaussian with A = 1 on
+// Pendulum.
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -49,11 +58,11 @@ namespace {
 
 constexpr int CL_MAX_H = 64;
 constexpr int CL_FAM_BOX = 0;  // DiagGaussian, A = 1: pd = (mean, logstd)
-constexpr int CL_FAM_CAT = 1;  // Categorical, K = 2: pd = 2 logits
+constexpr int CL_FAM_CAT = 1;  // Categorical, K = 2 or 3: pd = K logits
 
 struct ClassicArgs {
   const float* params;  // _rollout_weight_blob(): Wt[in][out], b per hidden
-                        // layer, Wv[H], bv, Wpt[H][2], bp
+                        // layer, Wv[H], bv, Wpt[H][P], bp
   int off_w[2], off_b[2], off_wv, off_bv, off_wp, off_bp;
   int H[2];             // hidden widths (H[1] unused with one layer)
   int activation;       // 1 tanh, 0 relu
@@ -103,8 +112,10 @@ DEV_INLINE float4 activate4(float4 z, int activation) {
 }
 
 // fold last-layer units j..j+3 (activations h) into the head accumulators
+// (p2 is touched only with P = 3)
+template <int P>
 DEV_INLINE void heads4(const float* lds, const ClassicLds& m, int j, float4 h,
-                       float& v, float& p0, float& p1) {
+                       float& v, float& p0, float& p1, float& p2) {
   const float4* hw = reinterpret_cast<const float4*>(lds + m.heads) + j;
   const float hh[4] = {h.x, h.y, h.z, h.w};
 #pragma unroll
@@ -113,6 +124,7 @@ DEV_INLINE void heads4(const float* lds, const ClassicLds& m, int j, float4 h,
     v = fmaf(w.x, hh[i], v);
     p0 = fmaf(w.y, hh[i], p0);
     p1 = fmaf(w.z, hh[i], p1);
+    if constexpr (P == 3) p2 = fmaf(w.w, hh[i], p2);
   }
 }
 
@@ -124,10 +136,10 @@ DEV_INLINE void heads4(const float* lds, const ClassicLds& m, int j, float4 h,
 // tile's independent chains are what hides the LDS latency: CartPole (64,64)
 // at E=65536 took 3.63 ms per rollout with 4-unit tiles only, 1.97 ms with
 // the 16-unit tile (profiles/r12_rollout_classic.txt).
-template <int JT>
+template <int JT, int P>
 DEV_INLINE void hidden2_tile(const float* lds, const ClassicLds& m,
                              const float* img, int j, int activation,
-                             float& v, float& p0, float& p1) {
+                             float& v, float& p0, float& p1, float& p2) {
   constexpr int Q = JT / 4;
   float4 z[Q];
 #pragma unroll
@@ -149,18 +161,19 @@ DEV_INLINE void hidden2_tile(const float* lds, const ClassicLds& m,
   }
 #pragma unroll
   for (int q = 0; q < Q; ++q)
-    heads4(lds, m, j + 4 * q, activate4(z[q], activation), v, p0, p1);
+    heads4<P>(lds, m, j + 4 * q, activate4(z[q], activation), v, p0, p1, p2);
 }
 
-// policy forward of one lane's observation x[D]: value and the two pd params
-template <int D, int NH>
+// policy forward of one lane's observation x[D]: value and the P pd params
+template <int D, int NH, int P>
 DEV_INLINE void classic_forward(float* lds, const ClassicLds& m,
                                 const float* x, int activation, float& v,
-                                float& p0, float& p1) {
+                                float& p0, float& p1, float& p2) {
   const float4 hb = *reinterpret_cast<const float4*>(lds + m.hb);
   v = hb.x;
   p0 = hb.y;
   p1 = hb.z;
+  if constexpr (P == 3) p2 = hb.w;
   float* img = lds + m.img + threadIdx.x;  // this lane's column
   for (int j = 0; j < m.h0p; j += 4) {
     float4 z = *reinterpret_cast<const float4*>(lds + m.b1 + j);
@@ -175,7 +188,7 @@ DEV_INLINE void classic_forward(float* lds, const ClassicLds& m,
     }
     z = activate4(z, activation);
     if constexpr (NH == 1) {
-      heads4(lds, m, j, z, v, p0, p1);
+      heads4<P>(lds, m, j, z, v, p0, p1, p2);
     } else {
       img[(j + 0) * WAVE] = z.x;
       img[(j + 1) * WAVE] = z.y;
@@ -188,9 +201,9 @@ DEV_INLINE void classic_forward(float* lds, const ClassicLds& m,
     // lane in program order, no barrier
     int j = 0;
     for (; j + 16 <= m.h1p; j += 16)
-      hidden2_tile<16>(lds, m, img, j, activation, v, p0, p1);
+      hidden2_tile<16, P>(lds, m, img, j, activation, v, p0, p1, p2);
     for (; j < m.h1p; j += 4)
-      hidden2_tile<4>(lds, m, img, j, activation, v, p0, p1);
+      hidden2_tile<4, P>(lds, m, img, j, activation, v, p0, p1, p2);
   }
 }
 
@@ -255,6 +268,7 @@ template <int FAM, int ENV, int NH>
 __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
   constexpr int S = ClassicEnv<ENV>::S;
   constexpr int D = ClassicEnv<ENV>::D;
+  constexpr int P = ClassicEnv<ENV>::P;
   extern __shared__ __align__(16) float lds[];
   const ClassicLds m = classic_lds<NH>(D, a.H[0], a.H[1]);
 
@@ -271,15 +285,16 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
   for (int j = threadIdx.x; j < hlp; j += blockDim.x) {
     const bool in = j < HL;
     lds[m.heads + 4 * j + 0] = in ? a.params[a.off_wv + j] : 0.f;
-    lds[m.heads + 4 * j + 1] = in ? a.params[a.off_wp + 2 * j] : 0.f;
-    lds[m.heads + 4 * j + 2] = in ? a.params[a.off_wp + 2 * j + 1] : 0.f;
-    lds[m.heads + 4 * j + 3] = 0.f;
+    lds[m.heads + 4 * j + 1] = in ? a.params[a.off_wp + P * j] : 0.f;
+    lds[m.heads + 4 * j + 2] = in ? a.params[a.off_wp + P * j + 1] : 0.f;
+    lds[m.heads + 4 * j + 3] =
+        (P == 3 && in) ? a.params[a.off_wp + P * j + P - 1] : 0.f;
   }
   if (threadIdx.x == 0) {
     lds[m.hb + 0] = a.params[a.off_bv];
     lds[m.hb + 1] = a.params[a.off_bp];
     lds[m.hb + 2] = a.params[a.off_bp + 1];
-    lds[m.hb + 3] = 0.f;
+    lds[m.hb + 3] = (P == 3) ? a.params[a.off_bp + P - 1] : 0.f;
   }
   __syncthreads();
 
@@ -298,7 +313,7 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
       o += 2 * TE;
     }
     float* states = o; o += TE * D;
-    float* pd = o; o += TE * 2;
+    float* pd = o; o += TE * P;
     if constexpr (FAM == CL_FAM_BOX) {
       act_f = o;
       o += TE;
@@ -309,6 +324,8 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
     float* boot = o;
     const bool states_vec =
         D == 4 && (reinterpret_cast<uintptr_t>(states) & 15) == 0;
+    const bool states_vec2 =
+        D == 6 && (reinterpret_cast<uintptr_t>(states) & 7) == 0;
     const bool pd_vec = (reinterpret_cast<uintptr_t>(pd) & 7) == 0;
 
     // ---- this lane's env --------------------------------------------------
@@ -329,13 +346,26 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
           row_stored = true;
         }
       }
+      if constexpr (D == 6) {
+        if (states_vec2) {
+          float2* row = reinterpret_cast<float2*>(states + i * 6);
+          row[0] = make_float2(x[0], x[1]);
+          row[1] = make_float2(x[2], x[3]);
+          row[2] = make_float2(x[4], x[5]);
+          row_stored = true;
+        }
+      }
       if (!row_stored) {
 #pragma unroll
         for (int d = 0; d < D; ++d) states[i * D + d] = x[d];
       }
-      float v, p0, p1;
-      classic_forward<D, NH>(lds, m, x, a.activation, v, p0, p1);
-      if (pd_vec) {
+      float v, p0, p1, p2;
+      classic_forward<D, NH, P>(lds, m, x, a.activation, v, p0, p1, p2);
+      if constexpr (P == 3) {
+        pd[i * 3] = p0;
+        pd[i * 3 + 1] = p1;
+        pd[i * 3 + 2] = p2;
+      } else if (pd_vec) {
         *reinterpret_cast<float2*>(pd + i * 2) = make_float2(p0, p1);
       } else {
         pd[i * 2] = p0;
@@ -345,7 +375,14 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
 
       float r;
       int done;
-      if constexpr (FAM == CL_FAM_CAT) {
+      if constexpr (FAM == CL_FAM_CAT && P == 3) {
+        int arg = mcat_draw(
+            [&](int c) { return c == 0 ? p0 : (c == 1 ? p1 : p2); }, 0, 3,
+            a.seed, e, step);
+        arg = mcat_explore(arg, 3, 0, a.seed, e, step, a.eps);
+        act_i64[i] = arg;
+        done = acrobot_step(s, arg, r);
+      } else if constexpr (FAM == CL_FAM_CAT) {
         int arg = mcat_draw([&](int c) { return c == 0 ? p0 : p1; }, 0, 2,
                             a.seed, e, step);
         arg = mcat_explore(arg, 2, 0, a.seed, e, step, a.eps);
@@ -376,8 +413,8 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
     }
 
     // ---- bootstrap value, persisted env state ------------------------------
-    float v, p0, p1;
-    classic_forward<D, NH>(lds, m, x, a.activation, v, p0, p1);
+    float v, p0, p1, p2;
+    classic_forward<D, NH, P>(lds, m, x, a.activation, v, p0, p1, p2);
     boot[e] = v;
 #pragma unroll
     for (int d = 0; d < S; ++d) a.s[(int64_t)e * S + d] = s[d];
@@ -393,7 +430,7 @@ bool f32_cuda(const torch::Tensor& t) {
   return t.is_cuda() && t.is_contiguous() && t.dtype() == torch::kFloat32;
 }
 
-// Shared body of the two bindings: checks, launch, blob views, moments.
+// Shared body of the bindings: checks, launch, blob views, moments.
 template <int FAM, int ENV>
 std::vector<torch::Tensor> classic_run(
     torch::Tensor params, std::vector<int64_t> offsets,
@@ -403,9 +440,12 @@ std::vector<torch::Tensor> classic_run(
     int64_t T, int64_t seed, torch::Tensor out_buf) {
   constexpr int S = ClassicEnv<ENV>::S;
   constexpr int D = ClassicEnv<ENV>::D;
-  TORCH_CHECK(env_id == ENV, FAM == CL_FAM_CAT
-                                 ? "classic_rollout_cat runs CartPole (env 0)"
-                                 : "classic_rollout_box runs Pendulum (env 1)");
+  constexpr int P = ClassicEnv<ENV>::P;
+  TORCH_CHECK(env_id == ENV,
+              FAM == CL_FAM_CAT
+                  ? "classic_rollout_cat runs CartPole (env 0) and Acrobot "
+                    "(env 2)"
+                  : "classic_rollout_box runs Pendulum (env 1)");
   const int nh = static_cast<int>(dims.size()) - 1;
   TORCH_CHECK(nh == 1 || nh == 2,
               "classic rollout supports 1 or 2 hidden layers");
@@ -451,9 +491,9 @@ std::vector<torch::Tensor> classic_run(
   const int64_t* ho = offsets.data() + 2 * nh;
   TORCH_CHECK(ho[0] >= 0 && ho[1] >= 0 && ho[2] >= 0 && ho[3] >= 0 &&
                   ho[0] + HL <= params.numel() && ho[1] + 1 <= params.numel() &&
-                  ho[2] + 2 * HL <= params.numel() &&
-                  ho[3] + 2 <= params.numel(),
-              "weight blob too small for the value and 2-wide policy heads");
+                  ho[2] + P * HL <= params.numel() &&
+                  ho[3] + P <= params.numel(),
+              "weight blob too small for the value and policy heads");
   a.off_wv = static_cast<int>(ho[0]);
   a.off_bv = static_cast<int>(ho[1]);
   a.off_wp = static_cast<int>(ho[2]);
@@ -471,13 +511,13 @@ std::vector<torch::Tensor> classic_run(
   a.act_low = static_cast<float>(act_low);
   a.act_high = static_cast<float>(act_high);
 
-  // the out blob layouts of rollout_run_cat / rollout_run with P = 2:
+  // the out blob layouts of rollout_run_cat (K = P) / rollout_run (A = 1):
   //   cat: actions(int64)[T*E] | states | logits | values | rewards | dones |
   //        boot | moments (the int64 region leads so it is 8-byte aligned)
   //   box: states | pdflat | actions | values | rewards | dones | boot |
   //        moments
   const int64_t n_out = (FAM == CL_FAM_CAT)
-                            ? T * E * (2 + D + 2 + 3) + E + 5
+                            ? T * E * (2 + D + P + 3) + E + 5
                             : T * E * (D + 3 + 3) + E + 5;
   torch::Tensor out = (out_buf.numel() == n_out)
                           ? out_buf
@@ -518,7 +558,7 @@ std::vector<torch::Tensor> classic_run(
     o = 2 * T * E;
   }
   auto states = take({T, E, (int64_t)D});
-  auto pdflats = take({T, E, 2});
+  auto pdflats = take({T, E, (int64_t)P});
   if (FAM == CL_FAM_BOX) actions = take({T, E, 1});
   auto values = take({T, E});
   auto rewards = take({T, E});
@@ -532,16 +572,26 @@ std::vector<torch::Tensor> classic_run(
 
 }  // namespace
 
-// CartPole under a Discrete(2) / Categorical policy.  Argument order follows
-// rollout_run_cat, with the synthetic env's (blob, rank, horizons, noise)
-// replaced by (env_id, s, time_limit).
+// CartPole under a Discrete(2), or Acrobot under a Discrete(3), Categorical
+// policy, chosen by env_id.  Argument order follows rollout_run_cat, with the
+// synthetic env's (blob, rank, horizons, noise) replaced by (env_id, s,
+// time_limit).
 std::vector<torch::Tensor> classic_rollout_cat(
     torch::Tensor params, std::vector<int64_t> offsets,
     std::vector<int64_t> dims, int64_t activation, int64_t env_id,
     torch::Tensor s, int64_t time_limit, double eps_explore, torch::Tensor x,
     torch::Tensor t, torch::Tensor epr, int64_t T, int64_t n_actions,
     int64_t seed, torch::Tensor out_buf) {
-  TORCH_CHECK(n_actions == 2, "classic_rollout_cat supports K = 2");
+  const bool cartpole = env_id == ENV_CARTPOLE && n_actions == 2;
+  const bool acrobot = env_id == ENV_ACROBOT && n_actions == 3;
+  TORCH_CHECK(cartpole || acrobot,
+              "classic_rollout_cat supports (env_id, n_actions) = (0, 2) "
+              "CartPole and (2, 3) Acrobot; got (", env_id, ", ", n_actions,
+              ")");
+  if (acrobot)
+    return classic_run<CL_FAM_CAT, ENV_ACROBOT>(
+        params, offsets, dims, activation, env_id, s, time_limit, 0.0, 0.0,
+        eps_explore, x, t, epr, T, seed, out_buf);
   return classic_run<CL_FAM_CAT, ENV_CARTPOLE>(
       params, offsets, dims, activation, env_id, s, time_limit, 0.0, 0.0,
       eps_explore, x, t, epr, T, seed, out_buf);

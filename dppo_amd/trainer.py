@@ -517,22 +517,32 @@ class DPPOEngine:
         # range -> on wherever eligible.  (Measured with the moments still
         # taken by ep_moments_kernel after the rollout; the in-kernel fold
         # that replaced it drops two launches and is not re-measured.)
+        # Acrobot (profiles/r13_rollout_acrobot.txt, same tool, CartPole
+        # alternated in the same process): (16,) eager 88.7 / 85.7 / 76.0 vs
+        # kernel 0.33 / 0.34 / 0.43; (64,64) 89.1 / 77.8 / 76.7 vs 1.61 /
+        # 1.62 / 2.22.  The kernel wins every alternated pair (34x at the
+        # least; widest spread 12.2 ms eager, 0.006 ms kernel) -> on wherever
+        # eligible.  RK4 costs 0.11-0.18 ms per rollout over CartPole's Euler
+        # step at the same shapes (0.19 / 0.19 / 0.24 and 1.48 / 1.51 / 2.03).
         # classic_rollout_kernel<FAM, ENV, NH> for gfx950 (FAM 0 Box / 1
-        # Categorical, ENV 0 CartPole / 1 Pendulum, NH hidden layers), no
-        # VGPR spills, scratch 0 in all four (<1,0,2> keeps 8 SGPRs in VGPR
-        # lanes):
+        # Categorical, ENV 0 CartPole / 1 Pendulum / 2 Acrobot, NH hidden
+        # layers), no VGPR spills, scratch 0 in all six (<1,0,2> keeps 8
+        # SGPRs in VGPR lanes):
         #   <1,0,1> VGPR  65 SGPR  91 LDS   592 B at (16,)    occ 7
         #   <1,0,2> VGPR 115 SGPR 106 LDS 35344 B at (64,64)  occ 4 (LDS: 1)
         #   <0,1,1> VGPR  65 SGPR  81 LDS   528 B at (16,)    occ 7
         #   <0,1,2> VGPR 120 SGPR 100 LDS 35088 B at (64,64)  occ 4 (LDS: 1)
+        #   <1,2,1> VGPR  74 SGPR  91 LDS   720 B at (16,)    occ 6
+        #   <1,2,2> VGPR 118 SGPR 104 LDS 35856 B at (64,64)  occ 4 (LDS: 1)
         return True
 
     @torch.no_grad()
     def _rollout_once_hip_classic(self) -> Tuple[RolloutBatch, Dict[str, float]]:
         """Physics rollout in a single launch, one lane per env
         (classic_rollout.hip): policy forward + sampling + epsilon overlay +
-        CartPole / Pendulum step + episode bookkeeping and resets for all T
-        steps, into the out blob layouts of rollout_run_cat / rollout_run."""
+        CartPole / Pendulum / Acrobot step + episode bookkeeping and resets
+        for all T steps, into the out blob layouts of rollout_run_cat (K =
+        the game's action count: 2 or 3) / rollout_run."""
         from .ops import hip_ext
 
         ext = hip_ext()

@@ -14,7 +14,8 @@ Worker (its rank's engine); rank 0 also builds the Chief facade; the
 Event/deque fabric is replaced by the synchronous RCCL round protocol.
 After training, a short greedy eval loop prints per-episode rewards
 (main.py:67-79 — finite by default instead of the reference's infinite
-render loop).
+render loop); with ENV_DYNAMICS='physics' it steps the game's real dynamics,
+as training did.
 """
 
 from __future__ import annotations
@@ -30,6 +31,7 @@ from dppo_amd import DPPOConfig
 from dppo_amd.chief import Chief
 from dppo_amd.checkpoint import save_state, load_state
 from dppo_amd.config import game_spaces
+from dppo_amd.envs.classic import CLASSIC_ENVS
 from dppo_amd.envs.synthetic import BatchedSyntheticEnv
 from dppo_amd.parallel.comm import Comm
 from dppo_amd.utils.coordinator import Coordinator
@@ -95,11 +97,17 @@ def main() -> None:
 
     # greedy eval loop (main.py:67-79), rank 0, finite
     if comm.rank == 0 and args.eval_episodes > 0 and chief is not None:
-        obs_space, act_space = game_spaces(cfg.GAME)
-        env = BatchedSyntheticEnv(
-            obs_space, act_space, num_envs=1, device=str(comm.device),
-            seed=cfg.SEED + 99991, horizon=max(cfg.MAX_EPOCH_STEPS // 2, 4),
-        )
+        if cfg.ENV_DYNAMICS == "physics":
+            # the env training ran on, with the game's own time limit
+            env = CLASSIC_ENVS[cfg.GAME](
+                1, device=str(comm.device), seed=cfg.SEED + 99991)
+        else:
+            obs_space, act_space = game_spaces(cfg.GAME)
+            env = BatchedSyntheticEnv(
+                obs_space, act_space, num_envs=1, device=str(comm.device),
+                seed=cfg.SEED + 99991,
+                horizon=max(cfg.MAX_EPOCH_STEPS // 2, 4),
+            )
         s = env.reset()
         epr, done_count = 0.0, 0
         while done_count < args.eval_episodes:

@@ -6,7 +6,8 @@ windows each, a device synchronise before every clock read); the table
 reports each arm's median window and its min..max spread.  Both arms include
 GAE and the rollout's single host sync.
 
-Usage: python tools/rollout_classic_ab.py [E ...]   (default 128 4096 65536)
+Usage: python tools/rollout_classic_ab.py [--games NAME,...] [E ...]
+       (default: every game; E = 128 4096 65536)
 """
 import os, statistics, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(
@@ -18,7 +19,8 @@ from dppo_amd.trainer import DPPOEngine
 T = 64
 REPEATS = 3
 SHAPES = [("CartPole-v0", (16,), "relu"), ("CartPole-v0", (64, 64), "tanh"),
-          ("Pendulum-v1", (16,), "relu")]
+          ("Pendulum-v1", (16,), "relu"),
+          ("Acrobot-v1", (16,), "relu"), ("Acrobot-v1", (64, 64), "tanh")]
 ARMS = [("eager", "0"), ("kernel", "1")]
 
 
@@ -33,10 +35,16 @@ def window(eng, knob, n):
 
 
 def main():
-    sizes = [int(a) for a in sys.argv[1:]] or [128, 4096, 65536]
+    argv = sys.argv[1:]
+    games = None
+    if argv and argv[0] == "--games":
+        games, argv = argv[1].split(","), argv[2:]
+    sizes = [int(a) for a in argv] or [128, 4096, 65536]
     print(f"# {torch.cuda.get_device_name(0)}; T={T}, {REPEATS} alternated "
           "windows per arm; ms per rollout_once(): median [min..max]")
     for game, hidden, act in SHAPES:
+        if games is not None and game not in games:
+            continue
         for E in sizes:
             cfg = DPPOConfig(GAME=game, ENV_DYNAMICS="physics",
                              HIDDEN_SIZES=hidden, ACTIVATION=act,
