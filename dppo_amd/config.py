@@ -63,7 +63,9 @@ REFERENCE_DEFAULTS: Dict[str, Any] = {
 
 #: games with real dynamics (envs/classic.py), selected by
 #: ENV_DYNAMICS='physics'; every other GAME is a synthetic shape preset only
-PHYSICS_GAMES: Tuple[str, ...] = ("CartPole-v0", "Pendulum-v1", "Acrobot-v1")
+PHYSICS_GAMES: Tuple[str, ...] = (
+    "CartPole-v0", "Pendulum-v1", "Acrobot-v1", "MountainCar-v0",
+    "MountainCarContinuous-v0", "CartPole-v1")
 
 
 @dataclass
@@ -191,7 +193,10 @@ class DPPOConfig:
 #: Others/distributions.py:231-243), so every family is trainable here
 GAME_SHAPES: Dict[str, Tuple[int, str, object]] = {
     "CartPole-v0": (4, "discrete", 2),
+    "CartPole-v1": (4, "discrete", 2),
     "Acrobot-v1": (6, "discrete", 3),
+    "MountainCar-v0": (2, "discrete", 3),
+    "MountainCarContinuous-v0": (2, "box", 1),
     "LunarLander-v2": (8, "discrete", 4),
     "Pendulum-v1": (3, "box", 1),
     "HalfCheetah-v4": (17, "box", 6),

@@ -1,5 +1,8 @@
-from .classic import BatchedAcrobot, BatchedCartPole, BatchedPendulum
+from .classic import (BatchedAcrobot, BatchedCartPole, BatchedCartPoleV1,
+                      BatchedMountainCar, BatchedMountainCarContinuous,
+                      BatchedPendulum)
 from .synthetic import BatchedSyntheticEnv, make_env
 
-__all__ = ["BatchedAcrobot", "BatchedCartPole", "BatchedPendulum",
-           "BatchedSyntheticEnv", "make_env"]
+__all__ = ["BatchedAcrobot", "BatchedCartPole", "BatchedCartPoleV1",
+           "BatchedMountainCar", "BatchedMountainCarContinuous",
+           "BatchedPendulum", "BatchedSyntheticEnv", "make_env"]

@@ -2,8 +2,8 @@
 training device.
 
 The reference steps gym's CartPole-v0 (reference main.py:13, Worker.py:10).
-CartPole, Pendulum and Acrobot are a dozen closed-form lines each, so they
-need no simulator: E envs per rank live as device tensors and step with batched torch
+CartPole, Pendulum, Acrobot and the two MountainCars are a dozen closed-form
+lines each, so they need no simulator: E envs per rank live as device tensors and step with batched torch
 ops (capture-safe, no host sync; this is also the CPU path) or inside the
 lane-per-env HIP rollout (ops/hip/classic_rollout.hip), whose device math in
 ops/hip/classic_env.h reproduces the float32 expressions below.
@@ -17,7 +17,14 @@ sin theta1, cos theta2, sin theta2, omega1, omega2), Discrete(3) giving a
 torque of -1 / 0 / +1 on the second joint, one RK4 step of gym's "book"
 dynamics per env step, reward -1 per step until the tip clears the bar
 (-cos theta1 - cos(theta1 + theta2) > 1), which terminates with reward 0.
-All truncate at `time_limit` steps (200, 200 and 500 by default).  As everywhere in this project the
+MountainCar-v0: state = observation = (position, velocity), Discrete(3)
+pushing left / not at all / right, reward -1 per step, terminates at
+position >= 0.5.  MountainCarContinuous-v0: the same hill under a
+Box(-1, 1, (1,)) force, terminates at position >= 0.45 with reward 100, and
+every step costs 0.1 a^2 of the raw action.  Both start at rest with the
+position uniform in (-0.6, -0.4].  CartPole-v1 is CartPole-v0 with a time
+limit of 500.
+All truncate at `time_limit` steps (200, 200, 500, 200 and 999 by default).  As everywhere in this project the
 observation returned on a done step is the fresh one and the reward belongs
 to the pre-reset transition.
 """
@@ -33,6 +40,7 @@ from ..config import DPPOConfig, game_spaces
 
 CARTPOLE, PENDULUM = 0, 1       # env ids of the HIP rollout bindings
 ACROBOT = 2
+MOUNTAINCAR, MOUNTAINCAR_CONT = 3, 4
 
 X_LIMIT = 2.4
 THETA_LIMIT = 0.20943951        # 12 degrees
@@ -138,6 +146,54 @@ def acrobot_obs(s: torch.Tensor) -> torch.Tensor:
                         torch.sin(th2), w1, w2], dim=-1)
 
 
+MC_MIN_POS, MC_MAX_POS = -1.2, 0.6
+MC_MAX_SPEED = 0.07
+
+
+def _shared_tail(p, v2, goal):
+    """The end of both MountainCar steps from the old position p and the new,
+    clamped velocity v2: the position is clamped to [-1.2, 0.6], the velocity
+    is zeroed where the car sits on the left wall still moving left, and the
+    episode terminates at position >= goal with a velocity >= 0:
+    (s' [N, 2], terminated [N] bool)."""
+    p2 = (p + v2).clamp(MC_MIN_POS, MC_MAX_POS)
+    v3 = torch.where((p2 == MC_MIN_POS) & (v2 < 0.0), torch.zeros_like(v2),
+                     v2)
+    term = (p2 >= goal) & (v3 >= 0.0)
+    return torch.stack([p2, v3], dim=-1), term
+
+
+def mountaincar_step(s: torch.Tensor, a: torch.Tensor):
+    """One step of MountainCar-v0 from states s [N, 2] = (position, velocity)
+    under actions a [N] in {0, 1, 2} (push left, none, right): (s' [N, 2],
+    reward [N], terminated [N] bool).  The reward is -1 on every step, the
+    terminating one included."""
+    p, v = s.unbind(-1)
+    push = a.reshape(-1).to(s.dtype) - 1.0
+    v2 = (v + push * 0.001 + torch.cos(3.0 * p) * (-0.0025)).clamp(
+        -MC_MAX_SPEED, MC_MAX_SPEED)
+    s2, term = _shared_tail(p, v2, 0.5)
+    return s2, -torch.ones_like(p), term
+
+
+def mountaincar_cont_step(s: torch.Tensor, a: torch.Tensor):
+    """One step of MountainCarContinuous-v0 from states s [N, 2] = (position,
+    velocity) under actions a [N] or [N, 1]: (s' [N, 2], reward [N],
+    terminated [N] bool).  The force is the action clipped to [-1, 1] here,
+    inside the physics, as in pendulum_step.  The reward is 100 on the
+    terminating step and 0 elsewhere, less 0.1 a^2 of the RAW, unclipped
+    action, as gym has it: the policy's sampler does not clip, so an action
+    outside [-1, 1] pushes no harder but costs more."""
+    p, v = s.unbind(-1)
+    a = a.reshape(-1).to(s.dtype)
+    f = a.clamp(-1.0, 1.0)
+    v2 = (v + f * 0.0015 - 0.0025 * torch.cos(3.0 * p)).clamp(
+        -MC_MAX_SPEED, MC_MAX_SPEED)
+    s2, term = _shared_tail(p, v2, 0.45)
+    reward = torch.where(term, 100.0, 0.0).to(s.dtype) - 0.1 * a * a
+    return s2, reward, term
+
+
 class BatchedClassicEnv:
     """E parallel physics envs on one device, with BatchedSyntheticEnv's
     vectorised API: reset() -> obs [E, obs_dim]; step(actions) -> (obs,
@@ -147,8 +203,11 @@ class BatchedClassicEnv:
     ENV_ID: int
     GAME: str
     S: int                      # state width
-    #: reset range per state dim: s_d uniform in (-RESET_HALF[d], RESET_HALF[d]]
+    #: reset range per state dim: s_d uniform in (RESET_CENTER[d] -
+    #: RESET_HALF[d], RESET_CENTER[d] + RESET_HALF[d]]; no RESET_CENTER means
+    #: all zero
     RESET_HALF: tuple
+    RESET_CENTER = None
     #: the game's registered episode length, the default `time_limit`
     TIME_LIMIT = 200
 
@@ -162,6 +221,10 @@ class BatchedClassicEnv:
         self.obs_dim = self.observation_space.shape[0]
         self._gen = torch.Generator(device=self.device.type).manual_seed(seed)
         self._half = torch.tensor(self.RESET_HALF, device=self.device)
+        center = self.RESET_CENTER
+        self._center = (
+            torch.tensor(center, device=self.device)
+            if center is not None and any(c != 0.0 for c in center) else None)
         self.horizons_i32 = torch.full(
             (num_envs,), self.time_limit, device=self.device,
             dtype=torch.int32)
@@ -181,7 +244,9 @@ class BatchedClassicEnv:
         # u in (0, 1], as the HIP rollout's rng_uniform
         u = 1.0 - torch.rand(self.num_envs, self.S, generator=self._gen,
                              device=self.device)
-        return (2.0 * u - 1.0) * self._half
+        s = (2.0 * u - 1.0) * self._half
+        # an all-zero centre is not added: the symmetric envs keep their bits
+        return s if self._center is None else self._center + s
 
     def reset(self) -> torch.Tensor:
         self.s = self.seed_state()
@@ -236,8 +301,44 @@ class BatchedAcrobot(BatchedClassicEnv):
         return acrobot_obs(s)
 
 
-CLASSIC_ENVS = {cls.GAME: cls for cls in (BatchedCartPole, BatchedPendulum,
-                                          BatchedAcrobot)}
+class BatchedCartPoleV1(BatchedCartPole):
+    """CartPole-v0's physics under CartPole-v1's time limit."""
+    GAME = "CartPole-v1"
+    TIME_LIMIT = 500
+
+    def __init__(self, num_envs: int, device: str = "cpu", seed: int = 0,
+                 time_limit: int = TIME_LIMIT):
+        super().__init__(num_envs, device=device, seed=seed,
+                         time_limit=time_limit)
+
+
+class BatchedMountainCar(BatchedClassicEnv):
+    ENV_ID, GAME, S = MOUNTAINCAR, "MountainCar-v0", 2
+    RESET_HALF = (0.1, 0.0)     # at rest
+    RESET_CENTER = (-0.5, 0.0)
+
+    def _physics(self, s, a):
+        return mountaincar_step(s, a)
+
+
+class BatchedMountainCarContinuous(BatchedClassicEnv):
+    ENV_ID, GAME, S = MOUNTAINCAR_CONT, "MountainCarContinuous-v0", 2
+    RESET_HALF = (0.1, 0.0)
+    RESET_CENTER = (-0.5, 0.0)
+    TIME_LIMIT = 999
+
+    def __init__(self, num_envs: int, device: str = "cpu", seed: int = 0,
+                 time_limit: int = TIME_LIMIT):
+        super().__init__(num_envs, device=device, seed=seed,
+                         time_limit=time_limit)
+
+    def _physics(self, s, a):
+        return mountaincar_cont_step(s, a)
+
+
+CLASSIC_ENVS = {cls.GAME: cls for cls in (
+    BatchedCartPole, BatchedPendulum, BatchedAcrobot, BatchedMountainCar,
+    BatchedMountainCarContinuous, BatchedCartPoleV1)}
 
 
 def make_classic_env(cfg: DPPOConfig, device: str,

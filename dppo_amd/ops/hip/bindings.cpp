@@ -244,12 +244,14 @@ std::vector<torch::Tensor> classic_rollout_box(
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("classic_rollout_cat", &classic_rollout_cat,
-          "lane-per-env T-step CartPole (env_id 0, Discrete(2)) or Acrobot "
-          "(env_id 2, Discrete(3), RK4) rollout, Categorical policy: MLP fwd + "
+          "lane-per-env T-step CartPole (env_id 0, Discrete(2)), Acrobot "
+          "(env_id 2, Discrete(3), RK4) or MountainCar (env_id 3, Discrete(3)) "
+          "rollout, Categorical policy: MLP fwd + "
           "Gumbel-max sample + physics step, int64 actions; rollout_run_cat's "
           "out blob with K = n_actions (gfx950)");
   mod.def("classic_rollout_box", &classic_rollout_box,
-          "lane-per-env T-step Pendulum rollout, Box(1)/DiagGaussian policy: "
+          "lane-per-env T-step Pendulum (env_id 1) or MountainCarContinuous "
+          "(env_id 4) rollout, Box(1)/DiagGaussian policy: "
           "MLP fwd + sample + physics step; rollout_run's out blob (gfx950)");
   mod.def("ppo_loss_cat_gh", &ppo_loss_cat_gh,
           "Categorical PPO loss gradient -> gh [B][ldgh] = [g_logits | g_v | "

@@ -1,7 +1,9 @@
-// Classic-control device math: the CartPole-v0, Pendulum-v1 and Acrobot-v1
-// transitions, their reset draws and observations, as functions of scalars.
+// Classic-control device math: the CartPole-v0, Pendulum-v1, Acrobot-v1,
+// MountainCar-v0 and MountainCarContinuous-v0 transitions, their reset draws
+// and observations, as functions of scalars.
 // The float32 expressions are those of envs/classic.py (cartpole_step,
-// pendulum_step, acrobot_step), which the tests hold the kernel to.  sinf / cosf / floorf are the accurate
+// pendulum_step, acrobot_step, mountaincar_step, mountaincar_cont_step),
+// which the tests hold the kernel to.  sinf / cosf / floorf are the accurate
 // forms on purpose: the state is integrated over hundreds of steps.
 // RNG, slot scheme and samplers are rollout_math.h's.
 #pragma once
@@ -11,9 +13,14 @@
 constexpr int ENV_CARTPOLE = 0;
 constexpr int ENV_PENDULUM = 1;
 constexpr int ENV_ACROBOT = 2;
+constexpr int ENV_MOUNTAINCAR = 3;
+constexpr int ENV_MOUNTAINCAR_CONT = 4;
 
-// per-env shapes: S state scalars, D observation scalars, P policy-head
-// columns (Categorical: the logits; DiagGaussian with A = 1: mean, logstd)
+// Per-env traits.  Shapes: S state scalars, D observation scalars, P
+// policy-head columns (Categorical: the logits; DiagGaussian with A = 1:
+// mean, logstd).  BOX: the policy is the DiagGaussian (else Categorical).
+// Reset: state dim d is drawn uniform in (center(d) - half(d), center(d) +
+// half(d)]; a dim with half 0 starts at its centre.
 template <int ENV>
 struct ClassicEnv;
 
@@ -22,6 +29,9 @@ struct ClassicEnv<ENV_CARTPOLE> {
   static constexpr int S = 4;  // x, x_dot, theta, theta_dot
   static constexpr int D = 4;  // the state itself
   static constexpr int P = 2;
+  static constexpr bool BOX = false;
+  static constexpr float reset_half(int) { return 0.05f; }
+  static constexpr float reset_center(int) { return 0.0f; }
 };
 
 template <>
@@ -29,6 +39,11 @@ struct ClassicEnv<ENV_PENDULUM> {
   static constexpr int S = 2;  // theta, theta_dot
   static constexpr int D = 3;  // cos theta, sin theta, theta_dot
   static constexpr int P = 2;
+  static constexpr bool BOX = true;
+  static constexpr float reset_half(int d) {
+    return d == 0 ? 3.1415926535897932f : 1.0f;
+  }
+  static constexpr float reset_center(int) { return 0.0f; }
 };
 
 template <>
@@ -36,6 +51,31 @@ struct ClassicEnv<ENV_ACROBOT> {
   static constexpr int S = 4;  // theta1, theta2, omega1, omega2
   static constexpr int D = 6;  // cos, sin of theta1; cos, sin of theta2; omegas
   static constexpr int P = 3;
+  static constexpr bool BOX = false;
+  static constexpr float reset_half(int) { return 0.1f; }
+  static constexpr float reset_center(int) { return 0.0f; }
+};
+
+// both MountainCars: the car starts at rest, position in (-0.6, -0.4]
+struct MountainCarReset {
+  static constexpr float reset_half(int d) { return d == 0 ? 0.1f : 0.0f; }
+  static constexpr float reset_center(int d) { return d == 0 ? -0.5f : 0.0f; }
+};
+
+template <>
+struct ClassicEnv<ENV_MOUNTAINCAR> : MountainCarReset {
+  static constexpr int S = 2;  // position, velocity
+  static constexpr int D = 2;  // the state itself
+  static constexpr int P = 3;
+  static constexpr bool BOX = false;
+};
+
+template <>
+struct ClassicEnv<ENV_MOUNTAINCAR_CONT> : MountainCarReset {
+  static constexpr int S = 2;
+  static constexpr int D = 2;
+  static constexpr int P = 2;  // mean, logstd
+  static constexpr bool BOX = true;
 };
 
 // One Euler step (tau = 0.02) under action a (1 pushes right, else left),
@@ -136,27 +176,69 @@ DEV_INLINE int acrobot_step(float* s, int a, float& reward) {
   return term;
 }
 
-// fresh state of a finished env: dim d uniform in (-half_d, half_d] from the
-// RNG_SLOT_RESET + d draw of (env, step)
+// The end of both MountainCar steps, from the old position p and the new,
+// clamped velocity v2 (_shared_tail of envs/classic.py): the position is
+// clamped to [-1.2, 0.6]; on the left wall a leftward velocity becomes 0;
+// returns the termination flag (position >= goal with a velocity >= 0).
+DEV_INLINE int mountaincar_tail(float* s, float p, float v2, float goal) {
+  const float p2 = fminf(fmaxf(p + v2, -1.2f), 0.6f);
+  const float v3 = (p2 == -1.2f && v2 < 0.0f) ? 0.0f : v2;
+  s[0] = p2;
+  s[1] = v3;
+  return (p2 >= goal && v3 >= 0.0f) ? 1 : 0;
+}
+
+// One step of MountainCar-v0 under action a in {0, 1, 2}: push left, not at
+// all, right.  Reward -1 on every step, the terminating one included;
+// returns the termination flag (position >= 0.5).
+DEV_INLINE int mountaincar_step(float* s, int a, float& reward) {
+  const float p = s[0], v = s[1];
+  const float push = (float)a - 1.0f;
+  const float v2 = fminf(
+      fmaxf(v + push * 0.001f + cosf(3.0f * p) * (-0.0025f), -0.07f), 0.07f);
+  reward = -1.0f;
+  return mountaincar_tail(s, p, v2, 0.5f);
+}
+
+// One step of MountainCarContinuous-v0 under the UNCLIPPED action a: the
+// force is clip(a, -1, 1), but the reward's 0.1 a^2 penalty takes the raw a,
+// as gym has it; 100 is added on the terminating step.  Returns the
+// termination flag (position >= 0.45).
+DEV_INLINE int mountaincar_cont_step(float* s, float a, float& reward) {
+  const float p = s[0], v = s[1];
+  const float f = fminf(fmaxf(a, -1.0f), 1.0f);
+  const float v2 = fminf(
+      fmaxf(v + f * 0.0015f - 0.0025f * cosf(3.0f * p), -0.07f), 0.07f);
+  const int term = mountaincar_tail(s, p, v2, 0.45f);
+  reward = (term ? 100.0f : 0.0f) - 0.1f * a * a;
+  return term;
+}
+
+// fresh state of a finished env: dim d uniform in (center_d - half_d,
+// center_d + half_d] from the RNG_SLOT_RESET + d draw of (env, step); a dim
+// of half-width 0 is its centre and draws nothing
 template <int ENV>
 DEV_INLINE void classic_reset(float* s, unsigned seed, int env, int step) {
+  using Env = ClassicEnv<ENV>;
 #pragma unroll
-  for (int d = 0; d < ClassicEnv<ENV>::S; ++d) {
-    const float half = (ENV == ENV_CARTPOLE)  ? 0.05f
-                       : (ENV == ENV_ACROBOT) ? 0.1f
-                       : (d == 0)             ? 3.1415926535897932f
-                                              : 1.0f;
+  for (int d = 0; d < Env::S; ++d) {
+    if (Env::reset_half(d) == 0.0f) {
+      s[d] = Env::reset_center(d);
+      continue;
+    }
     const float u = rng_uniform(seed, env, step, RNG_SLOT_RESET + d);
-    s[d] = (2.0f * u - 1.0f) * half;
+    const float z = (2.0f * u - 1.0f) * Env::reset_half(d);
+    // a zero centre is not added: the symmetric envs keep their expression
+    s[d] = (Env::reset_center(d) == 0.0f) ? z : Env::reset_center(d) + z;
   }
 }
 
 // observation of state s
 template <int ENV>
 DEV_INLINE void classic_obs(const float* s, float* x) {
-  if constexpr (ENV == ENV_CARTPOLE) {
+  if constexpr (ClassicEnv<ENV>::D == ClassicEnv<ENV>::S) {
 #pragma unroll
-    for (int d = 0; d < 4; ++d) x[d] = s[d];
+    for (int d = 0; d < ClassicEnv<ENV>::S; ++d) x[d] = s[d];
   } else if constexpr (ENV == ENV_ACROBOT) {
     sincosf(s[0], &x[1], &x[0]);
     sincosf(s[1], &x[3], &x[2]);

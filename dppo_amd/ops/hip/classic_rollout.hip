@@ -1,5 +1,6 @@
 // Classic-control rollout (gfx950): the whole T-step rollout of CartPole-v0,
-// Pendulum-v1 or Acrobot-v1 in one launch, ONE LANE PER ENV.
+// Pendulum-v1, Acrobot-v1, MountainCar-v0 or MountainCarContinuous-v0 in one
+// launch, ONE LANE PER ENV.
 //
 // A classic-control env is a handful of scalars, so rollout.hip's
 // decomposition (8 envs per 256-thread block, lanes split over the
@@ -29,23 +30,26 @@
 //   - The LAST hidden layer is never stored: each unit is folded into the
 //     1 + P head accumulators (v, p0, p1 and, for P = 3, p2) as it is
 //     produced.  P, the number of policy-head columns, is a compile-time
-//     property of the env (ClassicEnv<ENV>::P): 2 for CartPole (2 logits) and
-//     Pendulum (mean, logstd), 3 for Acrobot (3 logits).  Heads are staged as
+//     property of the env (ClassicEnv<ENV>::P): 2 for CartPole (2 logits),
+//     Pendulum and MountainCarContinuous (mean, logstd), 3 for Acrobot and
+//     MountainCar (3 logits).  Heads are staged as
 //     one float4 (Wv, Wp0, Wp1, Wp2 or 0) per unit, so P = 3 fills the lane
 //     that P = 2 pads and the LDS layout is the same for both.
 //   - The env step runs in scalar registers.  Acrobot's is one RK4 step: four
 //     derivative evaluations with their own sines and cosines
 //     (classic_env.h), about the cost of a (16,) trunk.
 // Per-step global writes have lane == env ([T][E] and [T][E][D] rows), so
-// they are coalesced by construction; 16-byte CartPole state rows and 8-byte
-// pd rows go out as one vector store, 24-byte Acrobot state rows as three
-// float2 stores, where the row base is aligned; 12-byte K = 3 pd rows go out
-// as scalars (lane stride 12 B is still a dense wave write).
+// they are coalesced by construction; 16-byte CartPole state rows, 8-byte
+// MountainCar state rows and 8-byte pd rows go out as one vector store,
+// 24-byte Acrobot state rows as three float2 stores, where the row base is
+// aligned; 12-byte K = 3 pd rows go out as scalars (lane stride 12 B is
+// still a dense wave write).
 //
 // Limits (checked in the bindings, mirrored by the engine's
 // _can_rollout_classic): 1-2 hidden layers of width <= 64; Categorical with
-// K = 2 on CartPole and K = 3 on Acrobot, DiagGaussian with A = 1 on
-// Pendulum.
+// K = 2 on CartPole and K = 3 on Acrobot and MountainCar, DiagGaussian with
+// A = 1 on Pendulum and MountainCarContinuous.  The family is a property of
+// the env (ClassicEnv<ENV>::BOX); the step inside the T loop is chosen by ENV.
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -269,6 +273,8 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
   constexpr int S = ClassicEnv<ENV>::S;
   constexpr int D = ClassicEnv<ENV>::D;
   constexpr int P = ClassicEnv<ENV>::P;
+  static_assert((FAM == CL_FAM_BOX) == ClassicEnv<ENV>::BOX,
+                "policy family and env do not go together");
   extern __shared__ __align__(16) float lds[];
   const ClassicLds m = classic_lds<NH>(D, a.H[0], a.H[1]);
 
@@ -325,7 +331,7 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
     const bool states_vec =
         D == 4 && (reinterpret_cast<uintptr_t>(states) & 15) == 0;
     const bool states_vec2 =
-        D == 6 && (reinterpret_cast<uintptr_t>(states) & 7) == 0;
+        (D == 6 || D == 2) && (reinterpret_cast<uintptr_t>(states) & 7) == 0;
     const bool pd_vec = (reinterpret_cast<uintptr_t>(pd) & 7) == 0;
 
     // ---- this lane's env --------------------------------------------------
@@ -355,6 +361,12 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
           row_stored = true;
         }
       }
+      if constexpr (D == 2) {
+        if (states_vec2) {
+          *reinterpret_cast<float2*>(states + i * 2) = make_float2(x[0], x[1]);
+          row_stored = true;
+        }
+      }
       if (!row_stored) {
 #pragma unroll
         for (int d = 0; d < D; ++d) states[i * D + d] = x[d];
@@ -375,24 +387,36 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
 
       float r;
       int done;
-      if constexpr (FAM == CL_FAM_CAT && P == 3) {
-        int arg = mcat_draw(
-            [&](int c) { return c == 0 ? p0 : (c == 1 ? p1 : p2); }, 0, 3,
-            a.seed, e, step);
-        arg = mcat_explore(arg, 3, 0, a.seed, e, step, a.eps);
+      if constexpr (FAM == CL_FAM_CAT) {
+        int arg;
+        if constexpr (P == 3) {
+          arg = mcat_draw(
+              [&](int c) { return c == 0 ? p0 : (c == 1 ? p1 : p2); }, 0, 3,
+              a.seed, e, step);
+        } else {
+          arg = mcat_draw([&](int c) { return c == 0 ? p0 : p1; }, 0, 2,
+                          a.seed, e, step);
+        }
+        arg = mcat_explore(arg, P, 0, a.seed, e, step, a.eps);
         act_i64[i] = arg;
-        done = acrobot_step(s, arg, r);
-      } else if constexpr (FAM == CL_FAM_CAT) {
-        int arg = mcat_draw([&](int c) { return c == 0 ? p0 : p1; }, 0, 2,
-                            a.seed, e, step);
-        arg = mcat_explore(arg, 2, 0, a.seed, e, step, a.eps);
-        act_i64[i] = arg;
-        done = cartpole_step(s, arg, r);
+        if constexpr (ENV == ENV_CARTPOLE) {
+          done = cartpole_step(s, arg, r);
+        } else if constexpr (ENV == ENV_ACROBOT) {
+          done = acrobot_step(s, arg, r);
+        } else {
+          static_assert(ENV == ENV_MOUNTAINCAR, "no step for this env");
+          done = mountaincar_step(s, arg, r);
+        }
       } else {
         const float act = box_sample(p0, p1, a.seed, e, step, 0, a.eps,
                                      a.act_low, a.act_high);
         act_f[i] = act;
-        done = pendulum_step(s, act, r);
+        if constexpr (ENV == ENV_PENDULUM) {
+          done = pendulum_step(s, act, r);
+        } else {
+          static_assert(ENV == ENV_MOUNTAINCAR_CONT, "no step for this env");
+          done = mountaincar_cont_step(s, act, r);
+        }
       }
       rewards[i] = r;
       ep += r;
@@ -443,9 +467,10 @@ std::vector<torch::Tensor> classic_run(
   constexpr int P = ClassicEnv<ENV>::P;
   TORCH_CHECK(env_id == ENV,
               FAM == CL_FAM_CAT
-                  ? "classic_rollout_cat runs CartPole (env 0) and Acrobot "
-                    "(env 2)"
-                  : "classic_rollout_box runs Pendulum (env 1)");
+                  ? "classic_rollout_cat runs CartPole (env 0), Acrobot "
+                    "(env 2) and MountainCar (env 3)"
+                  : "classic_rollout_box runs Pendulum (env 1) and "
+                    "MountainCarContinuous (env 4)");
   const int nh = static_cast<int>(dims.size()) - 1;
   TORCH_CHECK(nh == 1 || nh == 2,
               "classic rollout supports 1 or 2 hidden layers");
@@ -572,8 +597,8 @@ std::vector<torch::Tensor> classic_run(
 
 }  // namespace
 
-// CartPole under a Discrete(2), or Acrobot under a Discrete(3), Categorical
-// policy, chosen by env_id.  Argument order follows rollout_run_cat, with the
+// CartPole under a Discrete(2), or Acrobot or MountainCar under a
+// Discrete(3), Categorical policy, chosen by env_id.  Argument order follows rollout_run_cat, with the
 // synthetic env's (blob, rank, horizons, noise) replaced by (env_id, s,
 // time_limit).
 std::vector<torch::Tensor> classic_rollout_cat(
@@ -584,10 +609,15 @@ std::vector<torch::Tensor> classic_rollout_cat(
     int64_t seed, torch::Tensor out_buf) {
   const bool cartpole = env_id == ENV_CARTPOLE && n_actions == 2;
   const bool acrobot = env_id == ENV_ACROBOT && n_actions == 3;
-  TORCH_CHECK(cartpole || acrobot,
+  const bool mountaincar = env_id == ENV_MOUNTAINCAR && n_actions == 3;
+  TORCH_CHECK(cartpole || acrobot || mountaincar,
               "classic_rollout_cat supports (env_id, n_actions) = (0, 2) "
-              "CartPole and (2, 3) Acrobot; got (", env_id, ", ", n_actions,
-              ")");
+              "CartPole, (2, 3) Acrobot and (3, 3) MountainCar; got (", env_id,
+              ", ", n_actions, ")");
+  if (mountaincar)
+    return classic_run<CL_FAM_CAT, ENV_MOUNTAINCAR>(
+        params, offsets, dims, activation, env_id, s, time_limit, 0.0, 0.0,
+        eps_explore, x, t, epr, T, seed, out_buf);
   if (acrobot)
     return classic_run<CL_FAM_CAT, ENV_ACROBOT>(
         params, offsets, dims, activation, env_id, s, time_limit, 0.0, 0.0,
@@ -597,7 +627,8 @@ std::vector<torch::Tensor> classic_rollout_cat(
       eps_explore, x, t, epr, T, seed, out_buf);
 }
 
-// Pendulum under a Box(1) / DiagGaussian policy, after rollout_run.
+// Pendulum or MountainCarContinuous under a Box(1) / DiagGaussian policy,
+// chosen by env_id, after rollout_run.
 std::vector<torch::Tensor> classic_rollout_box(
     torch::Tensor params, std::vector<int64_t> offsets,
     std::vector<int64_t> dims, int64_t activation, int64_t env_id,
@@ -605,6 +636,13 @@ std::vector<torch::Tensor> classic_rollout_box(
     double eps_explore, torch::Tensor x, torch::Tensor t, torch::Tensor epr,
     int64_t T, int64_t act_dim, int64_t seed, torch::Tensor out_buf) {
   TORCH_CHECK(act_dim == 1, "classic_rollout_box supports A = 1");
+  TORCH_CHECK(env_id == ENV_PENDULUM || env_id == ENV_MOUNTAINCAR_CONT,
+              "classic_rollout_box supports env_id 1 Pendulum and 4 "
+              "MountainCarContinuous; got ", env_id);
+  if (env_id == ENV_MOUNTAINCAR_CONT)
+    return classic_run<CL_FAM_BOX, ENV_MOUNTAINCAR_CONT>(
+        params, offsets, dims, activation, env_id, s, time_limit, act_low,
+        act_high, eps_explore, x, t, epr, T, seed, out_buf);
   return classic_run<CL_FAM_BOX, ENV_PENDULUM>(
       params, offsets, dims, activation, env_id, s, time_limit, act_low,
       act_high, eps_explore, x, t, epr, T, seed, out_buf);

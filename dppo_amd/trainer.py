@@ -524,25 +524,43 @@ class DPPOEngine:
         # least; widest spread 12.2 ms eager, 0.006 ms kernel) -> on wherever
         # eligible.  RK4 costs 0.11-0.18 ms per rollout over CartPole's Euler
         # step at the same shapes (0.19 / 0.19 / 0.24 and 1.48 / 1.51 / 2.03).
+        # The MountainCars (profiles/r14_rollout_mountaincar.txt, same tool,
+        # CartPole alternated in the same process): MountainCar-v0 (16,)
+        # eager 29.2 / 29.4 / 29.1 vs kernel 0.16 / 0.17 / 0.21; (64,64)
+        # 30.7 / 31.2 / 34.0 vs 1.35 / 1.37 / 1.89; MountainCarContinuous-v0
+        # (16,) 31.9 / 32.0 / 31.6 vs 0.15 / 0.16 / 0.20.  The kernel wins
+        # every alternated pair (18x at the least; widest spread 3.6 ms
+        # eager, 0.005 ms kernel) -> on wherever eligible.  Both are faster
+        # than CartPole at the same trunk and E in that run (0.18 / 0.20 /
+        # 0.25 and 1.49 / 1.51 / 2.03), by more than either spread: one cosf
+        # and no division per step, 2 inputs to layer 1 instead of 4.
         # classic_rollout_kernel<FAM, ENV, NH> for gfx950 (FAM 0 Box / 1
-        # Categorical, ENV 0 CartPole / 1 Pendulum / 2 Acrobot, NH hidden
-        # layers), no VGPR spills, scratch 0 in all six (<1,0,2> keeps 8
-        # SGPRs in VGPR lanes):
+        # Categorical, ENV 0 CartPole / 1 Pendulum / 2 Acrobot / 3
+        # MountainCar / 4 MountainCarContinuous, NH hidden layers), no VGPR
+        # spills, scratch 0 in all ten (<1,0,2> keeps 8 SGPRs in VGPR
+        # lanes):
         #   <1,0,1> VGPR  65 SGPR  91 LDS   592 B at (16,)    occ 7
         #   <1,0,2> VGPR 115 SGPR 106 LDS 35344 B at (64,64)  occ 4 (LDS: 1)
         #   <0,1,1> VGPR  65 SGPR  81 LDS   528 B at (16,)    occ 7
         #   <0,1,2> VGPR 120 SGPR 100 LDS 35088 B at (64,64)  occ 4 (LDS: 1)
         #   <1,2,1> VGPR  74 SGPR  91 LDS   720 B at (16,)    occ 6
         #   <1,2,2> VGPR 118 SGPR 104 LDS 35856 B at (64,64)  occ 4 (LDS: 1)
+        #   <1,3,1> VGPR  62 SGPR  78 LDS   464 B at (16,)    occ 8
+        #   <1,3,2> VGPR 115 SGPR  99 LDS 34832 B at (64,64)  occ 4 (LDS: 1)
+        #   <0,4,1> VGPR  65 SGPR  83 LDS   464 B at (16,)    occ 7
+        #   <0,4,2> VGPR 118 SGPR 104 LDS 34832 B at (64,64)  occ 4 (LDS: 1)
         return True
 
     @torch.no_grad()
     def _rollout_once_hip_classic(self) -> Tuple[RolloutBatch, Dict[str, float]]:
         """Physics rollout in a single launch, one lane per env
         (classic_rollout.hip): policy forward + sampling + epsilon overlay +
-        CartPole / Pendulum / Acrobot step + episode bookkeeping and resets
-        for all T steps, into the out blob layouts of rollout_run_cat (K =
-        the game's action count: 2 or 3) / rollout_run."""
+        CartPole / Pendulum / Acrobot / MountainCar / MountainCarContinuous
+        step + episode bookkeeping and resets for all T steps, into the out
+        blob layouts of rollout_run_cat (K = the game's action count: 2 or
+        3) / rollout_run (A = 1).  The env is chosen by env.ENV_ID inside the
+        family's binding; D, the observation width (2 for both MountainCars),
+        sizes the blob here exactly as the bindings do."""
         from .ops import hip_ext
 
         ext = hip_ext()

@@ -20,7 +20,10 @@ T = 64
 REPEATS = 3
 SHAPES = [("CartPole-v0", (16,), "relu"), ("CartPole-v0", (64, 64), "tanh"),
           ("Pendulum-v1", (16,), "relu"),
-          ("Acrobot-v1", (16,), "relu"), ("Acrobot-v1", (64, 64), "tanh")]
+          ("Acrobot-v1", (16,), "relu"), ("Acrobot-v1", (64, 64), "tanh"),
+          ("MountainCar-v0", (16,), "relu"),
+          ("MountainCar-v0", (64, 64), "tanh"),
+          ("MountainCarContinuous-v0", (16,), "relu")]
 ARMS = [("eager", "0"), ("kernel", "1")]
 
 
