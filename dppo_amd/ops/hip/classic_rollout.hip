@@ -57,6 +57,7 @@
 
 #include "classic_env.h"
 #include "common.h"
+#include "rollout_blob.h"
 
 namespace {
 
@@ -310,6 +311,10 @@ __global__ __launch_bounds__(WAVE) void classic_rollout_kernel(ClassicArgs a) {
   const int e = blockIdx.x * WAVE + threadIdx.x;
   if (e < a.E) {  // no barrier below; tail lanes only join the reduction
     // ---- carve the output blob --------------------------------------------
+    // the layout rollout_blob.h defines (rollout_blob(T, E, D, P, 1, FAM ==
+    // CL_FAM_CAT)), spelled out here because taking the offsets from the
+    // struct changed the instructions of four of the ten instantiations
+    // (<0,4,2>, <1,0,2>, <1,3,1>, <1,3,2>: 2 to 42 lines each, same counts)
     const int64_t TE = (int64_t)a.T * a.E;
     float* o = a.out;
     int64_t* act_i64 = nullptr;
@@ -536,20 +541,9 @@ std::vector<torch::Tensor> classic_run(
   a.act_low = static_cast<float>(act_low);
   a.act_high = static_cast<float>(act_high);
 
-  // the out blob layouts of rollout_run_cat (K = P) / rollout_run (A = 1):
-  //   cat: actions(int64)[T*E] | states | logits | values | rewards | dones |
-  //        boot | moments (the int64 region leads so it is 8-byte aligned)
-  //   box: states | pdflat | actions | values | rewards | dones | boot |
-  //        moments
-  const int64_t n_out = (FAM == CL_FAM_CAT)
-                            ? T * E * (2 + D + P + 3) + E + 5
-                            : T * E * (D + 3 + 3) + E + 5;
-  torch::Tensor out = (out_buf.numel() == n_out)
-                          ? out_buf
-                          : torch::empty({n_out}, x.options());
-  TORCH_CHECK(f32_cuda(out), "out blob must be a contiguous f32 GPU tensor");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr<float>()) % 8 == 0,
-              "rollout output blob must be 8-byte aligned");
+  // the out blob layouts of rollout_run_cat (K = P) / rollout_run (A = 1)
+  const RolloutBlob blob = rollout_blob(T, E, D, P, 1, FAM == CL_FAM_CAT);
+  torch::Tensor out = rollout_blob_tensor(blob, out_buf, x);
   a.out = out.data_ptr<float>();
   const int nblocks = static_cast<int>((E + WAVE - 1) / WAVE);
   auto part = torch::empty({nblocks, 5}, x.options());
@@ -569,30 +563,10 @@ std::vector<torch::Tensor> classic_run(
                        lds_bytes, stream, a);
   }
 
-  int64_t o = 0;
-  auto take = [&](std::vector<int64_t> shape) {
-    int64_t n = 1;
-    for (auto sdim : shape) n *= sdim;
-    auto v = out.narrow(0, o, n).view(shape);
-    o += n;
-    return v;
-  };
-  torch::Tensor actions;
-  if (FAM == CL_FAM_CAT) {
-    actions = out.narrow(0, 0, 2 * T * E).view(torch::kInt64).view({T, E});
-    o = 2 * T * E;
-  }
-  auto states = take({T, E, (int64_t)D});
-  auto pdflats = take({T, E, (int64_t)P});
-  if (FAM == CL_FAM_BOX) actions = take({T, E, 1});
-  auto values = take({T, E});
-  auto rewards = take({T, E});
-  auto dones = take({T, E});
-  auto boot_v = take({E});
-  torch::Tensor moments = take({5});
+  auto views = rollout_blob_views(blob, out, FAM == CL_FAM_CAT);
   hipLaunchKernelGGL(classic_moments_kernel, dim3(1), block, 0, stream,
-                     a.part, nblocks, moments.data_ptr<float>());
-  return {states, pdflats, actions, values, rewards, dones, boot_v, moments};
+                     a.part, nblocks, views[7].data_ptr<float>());
+  return views;
 }
 
 }  // namespace

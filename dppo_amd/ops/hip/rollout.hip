@@ -50,6 +50,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "rollout_blob.h"
 #include "rollout_math.h"
 
 namespace {
@@ -84,11 +85,11 @@ struct LdsMap {
 };
 
 // P: pd-param width, actw: action slab width, partw: widest row the k-split
-// partial slab holds.  Box: (2A, A, Hmax).  Categorical: (K, 1,
-// max(Hmax, K+1)) — its K+1 head columns may exceed the trunk width.
-// MultiCategorical: (P, C, max(Hmax, P+1)); Bernoulli: (n, n, max(Hmax, n+1)).
-DEV_INLINE LdsMap lds_map(int D, int Hmax, int P, int actw, int partw,
-                          int rank, int et) {
+// partial slab holds (lds_map_for has each family's choice).  Host and
+// device: the launchers size the dynamic LDS from the map the kernel uses.
+__host__ __device__ __forceinline__ LdsMap lds_map(int D, int Hmax, int P,
+                                                   int actw, int partw,
+                                                   int rank, int et) {
   auto r4 = [](int v) { return (v + 3) & ~3; };
   LdsMap m;
   m.xs = r4(D);
@@ -108,6 +109,19 @@ DEV_INLINE LdsMap lds_map(int D, int Hmax, int P, int actw, int partw,
   m.racc = o; o += et;
   m.total = o;
   return m;
+}
+
+// The LDS map of a family with action width A (FAM_CAT: unused).  Box:
+// (actw, partw) = (A, Hmax).  Categorical: (1, max(Hmax, K+1)) — its K+1
+// head columns may exceed the trunk width.  MultiCategorical: (C,
+// max(Hmax, P+1)); Bernoulli: (n, max(Hmax, n+1)).
+template <int FAM>
+__host__ __device__ __forceinline__ LdsMap lds_map_for(int D, int Hmax, int P,
+                                                       int A, int rank,
+                                                       int et) {
+  const int actw = (FAM == FAM_CAT) ? 1 : A;
+  const int partw = (FAM == FAM_BOX || Hmax > P + 1) ? Hmax : P + 1;
+  return lds_map(D, Hmax, P, actw, partw, rank, et);
 }
 
 struct RolloutArgs {
@@ -204,11 +218,7 @@ __global__ void rollout_kernel(RolloutArgsOf<FAM> a) {
   const int ACT = TACT ? (TACT > 0 ? 1 : 0) : a.activation;
 
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const LdsMap lm = (FAM == FAM_CAT)
-                        ? lds_map(D, HMAX, P, 1, max(HMAX, P + 1), RNK, ET)
-                    : (FAM == FAM_BOX)
-                        ? lds_map(D, HMAX, P, A, HMAX, RNK, ET)
-                        : lds_map(D, HMAX, P, A, max(HMAX, P + 1), RNK, ET);
+  const LdsMap lm = lds_map_for<FAM>(D, HMAX, P, A, RNK, ET);
   const int X_OFF = lm.x, H0_OFF = lm.h0, H1_OFF = lm.h1, PD_OFF = lm.pd;
   const int ACT_OFF = lm.act, XV_OFF = lm.xv, PART_OFF = lm.part;
   const int MAX_D_S = lm.xs, MAX_H_S = lm.hs;
@@ -230,9 +240,12 @@ __global__ void rollout_kernel(RolloutArgsOf<FAM> a) {
   const float* env_Vt = env_d + D;
   const float* env_U = env_Vt + (int64_t)RNK * D;
   const float* env_B = env_U + (int64_t)RNK * D;
-  // output blob offsets (Categorical, MultiCategorical: the int64 action
-  // indices lead the blob so they are 8-byte aligned; no float action
-  // region.  Bernoulli: Box's layout with P = n)
+  // output blob regions: the layout rollout_blob.h defines (rollout_blob(T,
+  // E, D, P, actw, INT_ACT)), spelled out here because taking the offsets
+  // from the struct changed the generated code of 29 of the 30
+  // instantiations (two lines in five exact-shape ones, other instruction
+  // counts in 23 runtime-shape ones; 20 B of per-lane scratch gone from
+  // <1,2> and <3,2> Box and new in <4,2> Box and Categorical)
   constexpr bool INT_ACT = (FAM == FAM_CAT || FAM == FAM_MCAT);
   float* out_states =
       a.out + ((FAM == FAM_CAT)    ? 2 * (int64_t)T * E
@@ -927,157 +940,40 @@ static RolloutArgs rollout_args(
 }
 
 // DPPO_ROLLOUT_MW: absent -> -1 (auto, distinct from an explicit 0); see
-// rollout_run
+// rollout_min_waves
 static int rollout_mw_env() {
   static const int mw_env = env_int("DPPO_ROLLOUT_MW", -1);
   return mw_env;
 }
 
-std::vector<torch::Tensor> rollout_run(
-    torch::Tensor params, std::vector<int64_t> offsets,
-    std::vector<int64_t> dims, int64_t activation,
-    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
-    double noise, double act_low, double act_high, double eps_explore,
-    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
-    int64_t T, int64_t act_dim, int64_t seed, torch::Tensor out_buf,
-    int64_t ablate) {
-  const int64_t E = x.size(0);
-  const int64_t D = x.size(1);
-  const int A = static_cast<int>(act_dim);
-  TORCH_CHECK(A <= MAX_A, "dims exceed rollout-kernel limits");
-  RolloutArgs a = rollout_args(params, offsets, dims, activation, envblob,
-                               rank, horizons, noise, act_low, act_high,
-                               eps_explore, x, t, epr, T, act_dim, seed,
-                               ablate);
-  const int h_max = a.h_max;
-
-  const int P = 2 * A;
-  const int64_t n_out = T * E * (D + P + A + 3) + E + 5;
-  // caller may provide a persistent output blob (stable addresses for
-  // hipGraph capture of the downstream update)
-  torch::Tensor out = (out_buf.numel() == n_out)
-                          ? out_buf
-                          : torch::empty({n_out}, x.options());
-  auto epr_in = epr.clone();
-  a.out = out.data_ptr<float>();
-
-  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
-  // tiny-E: 2 envs per block -> 4x the blocks (E=64 fills 32 CUs instead
-  // of 8) AND a ~4x shorter per-phase issue chain (the per-lane env
-  // unrolls shrink); large E keeps the 8-env tile (ILP beats occupancy
-  // once the grid fills the chip)
-  const int et = ((E + ENV_TILE - 1) / ENV_TILE < 128 && E % 2 == 0) ? 2
-                                                                     : ENV_TILE;
-  const int grid = static_cast<int>((E + et - 1) / et);
-  auto r4 = [](int v) { return (v + 3) & ~3; };
-  const size_t lds_bytes =
-      (et * (r4((int)D) + 2 * r4(h_max) + r4(2 * A) + r4(A) +
-             r4((int)rank) + 4) +
-       NWAVES * et * r4(h_max)) *
-      sizeof(float);
-  // MINWAVES=4 measured 24.8 ms vs 27.7 ms at MINWAVES=3 (65k envs):
-  // the 4th wave/SIMD buys more than the 29-VGPR spill costs.  Below
-  // ~1 block/CU (tiny-E configs: BASELINE #2/#4) occupancy is grid-bound
-  // anyway, so MINWAVES=1 lifts the 128-VGPR cap — no spills, no
-  // per-lane scratch on the latency-critical per-step chain.
-  // DPPO_ROLLOUT_MW: absent -> auto (small grids get the unconstrained
-  // 1-wave/SIMD minimum, big grids the 4-wave one); explicit values pick
-  // the __launch_bounds__ min-waves instantiation: >=4 -> <4>, 2..3 ->
-  // <3>, 0..1 -> <1> (0 = "no minimum" = the 128-VGPR-cap-lifted kernel).
-  const int mw_env = rollout_mw_env();
-  const int mw = mw_env >= 0 ? mw_env : (grid <= N_CU ? 1 : 4);
-  // exact-shape specializations for the BASELINE families (index maps,
-  // trip counts and the LDS map constant-folded)
-  const bool full_tiles = (a.E % et) == 0;  // nE folds to the tile
-  const bool hc_shape = full_tiles && (a.D == 17 && a.h_max == 64 &&
-                         a.act_dim == 6 && a.n_hidden == 2 &&
-                         a.rank == 16 && a.activation == 1);
-  const bool hum_shape = full_tiles && (a.D == 376 && a.h_max == 64 &&
-                          a.act_dim == 17 && a.n_hidden == 2 &&
-                          a.rank == 16 && a.activation == 1);
-  if (mw >= 4) {
-    if (hc_shape && et == 8)
-      hipLaunchKernelGGL((rollout_kernel<4, 8, 17, 64, 6, 2, 16, 1>),
-                         dim3(grid), dim3(NWAVES * WAVE), lds_bytes, stream,
-                         a);
-    else if (hum_shape && et == 8)
-      hipLaunchKernelGGL((rollout_kernel<4, 8, 376, 64, 17, 2, 16, 1>),
-                         dim3(grid), dim3(NWAVES * WAVE), lds_bytes, stream,
-                         a);
-    else if (et == 2)
-      hipLaunchKernelGGL((rollout_kernel<4, 2>), dim3(grid),
-                         dim3(NWAVES * WAVE), lds_bytes, stream, a);
-    else
-      hipLaunchKernelGGL(rollout_kernel<4>, dim3(grid), dim3(NWAVES * WAVE),
-                         lds_bytes, stream, a);
-  } else if (mw >= 2) {
-    if (et == 2)
-      hipLaunchKernelGGL((rollout_kernel<3, 2>), dim3(grid),
-                         dim3(NWAVES * WAVE), lds_bytes, stream, a);
-    else
-      hipLaunchKernelGGL(rollout_kernel<3>, dim3(grid), dim3(NWAVES * WAVE),
-                         lds_bytes, stream, a);
-  } else {
-    if (hc_shape && et == 2)
-      hipLaunchKernelGGL((rollout_kernel<1, 2, 17, 64, 6, 2, 16, 1>),
-                         dim3(grid), dim3(NWAVES * WAVE), lds_bytes, stream,
-                         a);
-    else if (hum_shape && et == 2)
-      hipLaunchKernelGGL((rollout_kernel<1, 2, 376, 64, 17, 2, 16, 1>),
-                         dim3(grid), dim3(NWAVES * WAVE), lds_bytes, stream,
-                         a);
-    else if (hc_shape)
-      hipLaunchKernelGGL((rollout_kernel<1, 8, 17, 64, 6, 2, 16, 1>),
-                         dim3(grid), dim3(NWAVES * WAVE), lds_bytes, stream,
-                         a);
-    else if (hum_shape)
-      hipLaunchKernelGGL((rollout_kernel<1, 8, 376, 64, 17, 2, 16, 1>),
-                         dim3(grid), dim3(NWAVES * WAVE), lds_bytes, stream,
-                         a);
-    else if (et == 2)
-      hipLaunchKernelGGL((rollout_kernel<1, 2>), dim3(grid),
-                         dim3(NWAVES * WAVE), lds_bytes, stream, a);
-    else
-      hipLaunchKernelGGL(rollout_kernel<1>, dim3(grid), dim3(NWAVES * WAVE),
-                         lds_bytes, stream, a);
-  }
-
-  // carve views out of the blob
-  int64_t o = 0;
-  auto take = [&](std::vector<int64_t> shape) {
-    int64_t n = 1;
-    for (auto sdim : shape) n *= sdim;
-    auto v = out.narrow(0, o, n).view(shape);
-    o += n;
-    return v;
-  };
-  auto states = take({T, E, D});
-  auto pdflats = take({T, E, (int64_t)P});
-  auto actions = take({T, E, (int64_t)A});
-  auto values = take({T, E});
-  auto rewards = take({T, E});
-  auto dones = take({T, E});
-  auto boot_v = take({E});
-  auto moments = take({5});
-  moments.zero_();
-
-  hipLaunchKernelGGL(ep_moments_kernel,
-                     dim3(static_cast<int>((E + 255) / 256)), dim3(256), 0,
-                     stream, rewards.data_ptr<float>(), dones.data_ptr<float>(),
-                     epr_in.data_ptr<float>(), moments.data_ptr<float>(), T, E);
-  hipLaunchKernelGGL(ep_moments_decode_kernel, dim3(1), dim3(1), 0, stream,
-                     moments.data_ptr<float>());
-  return {states, pdflats, actions, values, rewards, dones, boot_v, moments};
+// Env tile of a launch.  tiny-E: 2 envs per block -> 4x the blocks (E=64
+// fills 32 CUs instead of 8) AND a ~4x shorter per-phase issue chain (the
+// per-lane env unrolls shrink); large E keeps the 8-env tile (ILP beats
+// occupancy once the grid fills the chip).  The grid is ceil(E / tile).
+static int rollout_env_tile(int64_t E) {
+  return ((E + ENV_TILE - 1) / ENV_TILE < 128 && E % 2 == 0) ? 2 : ENV_TILE;
 }
 
-// Launch selection of the runtime-shape logit families (FAM_CAT, FAM_MCAT,
-// FAM_BERN), following rollout_run: min-waves 1 for grids within one block
-// per CU, else 4, unless DPPO_ROLLOUT_MW picks; 2- or 8-env tiles.
+// MINWAVES=4 measured 24.8 ms vs 27.7 ms at MINWAVES=3 (65k envs):
+// the 4th wave/SIMD buys more than the 29-VGPR spill costs.  Below
+// ~1 block/CU (tiny-E configs: BASELINE #2/#4) occupancy is grid-bound
+// anyway, so MINWAVES=1 lifts the 128-VGPR cap — no spills, no
+// per-lane scratch on the latency-critical per-step chain.
+// DPPO_ROLLOUT_MW: absent -> auto (small grids get the unconstrained
+// 1-wave/SIMD minimum, big grids the 4-wave one); explicit values pick
+// the __launch_bounds__ min-waves instantiation: >=4 -> <4>, 2..3 ->
+// <3>, 0..1 -> <1> (0 = "no minimum" = the 128-VGPR-cap-lifted kernel).
+static int rollout_min_waves(int grid) {
+  const int mw_env = rollout_mw_env();
+  return mw_env >= 0 ? mw_env : (grid <= N_CU ? 1 : 4);
+}
+
+// Launch selection of the runtime-shape instantiations of a family: 2- or
+// 8-env tiles at the min-waves rollout_min_waves picks.
 template <int FAM>
 static void launch_rollout_fam(const RolloutArgsOf<FAM>& a, int grid, int et,
                                size_t lds_bytes, hipStream_t stream) {
-  const int mw_env = rollout_mw_env();
-  const int mw = mw_env >= 0 ? mw_env : (grid <= N_CU ? 1 : 4);
+  const int mw = rollout_min_waves(grid);
   const dim3 g(grid), b(NWAVES * WAVE);
   if (mw >= 4) {
     if (et == 2)
@@ -1103,10 +999,112 @@ static void launch_rollout_fam(const RolloutArgsOf<FAM>& a, int grid, int et,
   }
 }
 
+// Exact-shape Box specializations for the BASELINE families (index maps,
+// trip counts and the LDS map constant-folded): HalfCheetah and Humanoid
+// shapes on full tiles, at min-waves 4 (8-env tile) and 1 (both tiles).
+// False when this launch has none; the runtime-shape kernel takes it then.
+static bool launch_rollout_exact(const RolloutArgs& a, int grid, int et,
+                                 size_t lds_bytes, hipStream_t stream) {
+  const bool trunk = (a.E % et) == 0 &&  // nE folds to the tile
+                     a.h_max == 64 && a.n_hidden == 2 && a.rank == 16 &&
+                     a.activation == 1;
+  const bool hc = trunk && a.D == 17 && a.act_dim == 6;
+  const bool hum = trunk && a.D == 376 && a.act_dim == 17;
+  const int mw = rollout_min_waves(grid);
+  if (!(hc || hum) || (mw >= 4 ? et != 8 : mw >= 2)) return false;
+  const dim3 g(grid), b(NWAVES * WAVE);
+  if (mw >= 4) {
+    if (hc)
+      hipLaunchKernelGGL((rollout_kernel<4, 8, 17, 64, 6, 2, 16, 1>), g, b,
+                         lds_bytes, stream, a);
+    else
+      hipLaunchKernelGGL((rollout_kernel<4, 8, 376, 64, 17, 2, 16, 1>), g, b,
+                         lds_bytes, stream, a);
+  } else if (et == 2) {
+    if (hc)
+      hipLaunchKernelGGL((rollout_kernel<1, 2, 17, 64, 6, 2, 16, 1>), g, b,
+                         lds_bytes, stream, a);
+    else
+      hipLaunchKernelGGL((rollout_kernel<1, 2, 376, 64, 17, 2, 16, 1>), g, b,
+                         lds_bytes, stream, a);
+  } else {
+    if (hc)
+      hipLaunchKernelGGL((rollout_kernel<1, 8, 17, 64, 6, 2, 16, 1>), g, b,
+                         lds_bytes, stream, a);
+    else
+      hipLaunchKernelGGL((rollout_kernel<1, 8, 376, 64, 17, 2, 16, 1>), g, b,
+                         lds_bytes, stream, a);
+  }
+  return true;
+}
+
+// Episode moments of a rollout from its rewards/dones streams, into the
+// zeroed [5] `moments`.
+static void launch_ep_moments(const torch::Tensor& rewards,
+                              const torch::Tensor& dones,
+                              const torch::Tensor& epr_in,
+                              torch::Tensor& moments, int64_t T, int64_t E,
+                              hipStream_t stream) {
+  hipLaunchKernelGGL(ep_moments_kernel,
+                     dim3(static_cast<int>((E + 255) / 256)), dim3(256), 0,
+                     stream, rewards.data_ptr<float>(), dones.data_ptr<float>(),
+                     epr_in.data_ptr<float>(), moments.data_ptr<float>(), T, E);
+  hipLaunchKernelGGL(ep_moments_decode_kernel, dim3(1), dim3(1), 0, stream,
+                     moments.data_ptr<float>());
+}
+
+// Shared tail of the four bindings, after their checks filled `a`: the
+// output blob (rollout_blob.h; out_buf when the caller sized it exactly),
+// tile, grid and LDS size, the launch, the blob's views and the moments.
+template <int FAM>
+static std::vector<torch::Tensor> rollout_launch(
+    RolloutArgsOf<FAM>& a, int64_t P, const torch::Tensor& x,
+    const torch::Tensor& epr, const torch::Tensor& out_buf) {
+  const int64_t T = a.T, E = a.E;
+  const RolloutBlob blob =
+      rollout_blob(T, E, a.D, P, FAM == FAM_CAT ? 1 : a.act_dim,
+                   FAM == FAM_CAT || FAM == FAM_MCAT);
+  torch::Tensor out = rollout_blob_tensor(blob, out_buf, x);
+  auto epr_in = epr.clone();
+  a.out = out.data_ptr<float>();
+
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  const int et = rollout_env_tile(E);
+  const int grid = static_cast<int>((E + et - 1) / et);
+  const size_t lds_bytes =
+      lds_map_for<FAM>(a.D, a.h_max, static_cast<int>(P), a.act_dim, a.rank,
+                       et).total * sizeof(float);
+  bool launched = false;
+  if constexpr (FAM == FAM_BOX)
+    launched = launch_rollout_exact(a, grid, et, lds_bytes, stream);
+  if (!launched) launch_rollout_fam<FAM>(a, grid, et, lds_bytes, stream);
+
+  auto views = rollout_blob_views(blob, out, FAM == FAM_CAT);
+  views[7].zero_();
+  launch_ep_moments(views[4], views[5], epr_in, views[7], T, E, stream);
+  return views;
+}
+
+std::vector<torch::Tensor> rollout_run(
+    torch::Tensor params, std::vector<int64_t> offsets,
+    std::vector<int64_t> dims, int64_t activation,
+    torch::Tensor envblob, int64_t rank, torch::Tensor horizons,
+    double noise, double act_low, double act_high, double eps_explore,
+    torch::Tensor x, torch::Tensor t, torch::Tensor epr,
+    int64_t T, int64_t act_dim, int64_t seed, torch::Tensor out_buf,
+    int64_t ablate) {
+  TORCH_CHECK(act_dim <= MAX_A, "dims exceed rollout-kernel limits");
+  RolloutArgs a = rollout_args(params, offsets, dims, activation, envblob,
+                               rank, horizons, noise, act_low, act_high,
+                               eps_explore, x, t, epr, T, act_dim, seed,
+                               ablate);
+  return rollout_launch<FAM_BOX>(a, 2 * act_dim, x, epr, out_buf);
+}
+
 // Discrete/Categorical whole-rollout: the FAM_CAT instantiations of
 // rollout_kernel (K logits + value heads, Gumbel-max sampling, uniform-index
 // epsilon overlay, a_in = B[a] row gather, int64 action indices written by
-// the kernel).  Launch selection follows rollout_run; runtime shapes only.
+// the kernel).  Launch selection is rollout_launch's; runtime shapes only.
 std::vector<torch::Tensor> rollout_run_cat(
     torch::Tensor params, std::vector<int64_t> offsets,
     std::vector<int64_t> dims, int64_t activation,
@@ -1123,7 +1121,6 @@ std::vector<torch::Tensor> rollout_run_cat(
   RolloutArgs a = rollout_args(params, offsets, dims, activation, envblob,
                                rank, horizons, noise, 0.0, 0.0, eps_explore,
                                x, t, epr, T, n_actions, seed, ablate);
-  const int h_max = a.h_max;
   TORCH_CHECK(envblob.is_cuda() && envblob.is_contiguous() &&
                   envblob.dtype() == torch::kFloat32 &&
                   envblob.numel() == D + 2 * rank * D + (int64_t)K * D,
@@ -1134,58 +1131,7 @@ std::vector<torch::Tensor> rollout_run_cat(
                   params.numel() >= offsets[2 * a.n_hidden + 3] + K,
               "weight blob too small for the K-wide policy head");
 
-  // blob: actions(int64)[T*E] | states | logits | values | rewards | dones |
-  // boot | moments, in floats (the int64 region is 2*T*E floats wide and
-  // leads the blob so it is 8-byte aligned)
-  const int64_t n_out = T * E * (2 + D + K + 3) + E + 5;
-  torch::Tensor out = (out_buf.numel() == n_out)
-                          ? out_buf
-                          : torch::empty({n_out}, x.options());
-  TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kFloat32 &&
-              out.is_contiguous());
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr<float>()) % 8 == 0,
-              "rollout output blob must be 8-byte aligned");
-  auto epr_in = epr.clone();
-  a.out = out.data_ptr<float>();
-
-  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
-  const int et = ((E + ENV_TILE - 1) / ENV_TILE < 128 && E % 2 == 0) ? 2
-                                                                     : ENV_TILE;
-  const int grid = static_cast<int>((E + et - 1) / et);
-  auto r4 = [](int v) { return (v + 3) & ~3; };
-  // mirrors the FAM_CAT lds_map: the k-split partial rows are sized for
-  // the K+1 head columns when those exceed the trunk width
-  const size_t lds_bytes =
-      (et * (r4((int)D) + 2 * r4(h_max) + r4(K) + r4(1) + r4((int)rank) + 4) +
-       NWAVES * et * r4(std::max(h_max, K + 1))) *
-      sizeof(float);
-  launch_rollout_fam<FAM_CAT>(a, grid, et, lds_bytes, stream);
-
-  auto actions = out.narrow(0, 0, 2 * T * E).view(torch::kInt64).view({T, E});
-  int64_t o = 2 * T * E;
-  auto take = [&](std::vector<int64_t> shape) {
-    int64_t n = 1;
-    for (auto sdim : shape) n *= sdim;
-    auto v = out.narrow(0, o, n).view(shape);
-    o += n;
-    return v;
-  };
-  auto states = take({T, E, D});
-  auto pdflats = take({T, E, (int64_t)K});
-  auto values = take({T, E});
-  auto rewards = take({T, E});
-  auto dones = take({T, E});
-  auto boot_v = take({E});
-  auto moments = take({5});
-  moments.zero_();
-
-  hipLaunchKernelGGL(ep_moments_kernel,
-                     dim3(static_cast<int>((E + 255) / 256)), dim3(256), 0,
-                     stream, rewards.data_ptr<float>(), dones.data_ptr<float>(),
-                     epr_in.data_ptr<float>(), moments.data_ptr<float>(), T, E);
-  hipLaunchKernelGGL(ep_moments_decode_kernel, dim3(1), dim3(1), 0, stream,
-                     moments.data_ptr<float>());
-  return {states, pdflats, actions, values, rewards, dones, boot_v, moments};
+  return rollout_launch<FAM_CAT>(a, K, x, epr, out_buf);
 }
 
 // MultiDiscrete/MultiCategorical (FAM_MCAT: act_w = C components, moff =
@@ -1211,7 +1157,6 @@ static std::vector<torch::Tensor> rollout_run_multi(
                    ablate);
   if constexpr (FAM == FAM_MCAT)
     for (size_t c = 0; c < moff.size(); ++c) a.moff[c] = moff[c];
-  const int h_max = a.h_max;
   TORCH_CHECK(T >= 1 && E >= 1 && params.is_cuda());
   TORCH_CHECK(envblob.is_cuda() && envblob.is_contiguous() &&
                   envblob.dtype() == torch::kFloat32 &&
@@ -1225,69 +1170,7 @@ static std::vector<torch::Tensor> rollout_run_multi(
                   params.numel() >= offsets[2 * a.n_hidden + 3] + P,
               "weight blob too small for the P-wide policy head");
 
-  // FAM_MCAT blob: actions(int64)[T*E*C] | states | logits | values |
-  // rewards | dones | boot | moments, in floats (the int64 region is
-  // 2*T*E*C floats wide and leads the blob so it is 8-byte aligned).
-  // FAM_BERN: Box's layout, states | logits | actions | values | ...
-  const int64_t n_out = (FAM == FAM_MCAT)
-                            ? T * E * (2 * act_w + D + P + 3) + E + 5
-                            : T * E * (D + P + act_w + 3) + E + 5;
-  torch::Tensor out = (out_buf.numel() == n_out)
-                          ? out_buf
-                          : torch::empty({n_out}, x.options());
-  TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kFloat32 &&
-              out.is_contiguous());
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr<float>()) % 8 == 0,
-              "rollout output blob must be 8-byte aligned");
-  auto epr_in = epr.clone();
-  a.out = out.data_ptr<float>();
-
-  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
-  const int et = ((E + ENV_TILE - 1) / ENV_TILE < 128 && E % 2 == 0) ? 2
-                                                                     : ENV_TILE;
-  const int grid = static_cast<int>((E + et - 1) / et);
-  auto r4 = [](int v) { return (v + 3) & ~3; };
-  // mirrors the kernel's lds_map for these families
-  const size_t lds_bytes =
-      (et * (r4((int)D) + 2 * r4(h_max) + r4((int)P) + r4((int)act_w) +
-             r4((int)rank) + 4) +
-       NWAVES * et * r4(std::max(h_max, (int)P + 1))) *
-      sizeof(float);
-  launch_rollout_fam<FAM>(a, grid, et, lds_bytes, stream);
-
-  int64_t o = 0;
-  auto take = [&](std::vector<int64_t> shape) {
-    int64_t n = 1;
-    for (auto sdim : shape) n *= sdim;
-    auto v = out.narrow(0, o, n).view(shape);
-    o += n;
-    return v;
-  };
-  torch::Tensor actions;
-  if (FAM == FAM_MCAT) {
-    actions = out.narrow(0, 0, 2 * T * E * act_w)
-                  .view(torch::kInt64)
-                  .view({T, E, act_w});
-    o = 2 * T * E * act_w;
-  }
-  // (typed: the lambda's result is a dependent type in this template)
-  torch::Tensor states = take({T, E, D});
-  torch::Tensor pdflats = take({T, E, P});
-  if (FAM == FAM_BERN) actions = take({T, E, act_w});
-  torch::Tensor values = take({T, E});
-  torch::Tensor rewards = take({T, E});
-  torch::Tensor dones = take({T, E});
-  torch::Tensor boot_v = take({E});
-  torch::Tensor moments = take({5});
-  moments.zero_();
-
-  hipLaunchKernelGGL(ep_moments_kernel,
-                     dim3(static_cast<int>((E + 255) / 256)), dim3(256), 0,
-                     stream, rewards.data_ptr<float>(), dones.data_ptr<float>(),
-                     epr_in.data_ptr<float>(), moments.data_ptr<float>(), T, E);
-  hipLaunchKernelGGL(ep_moments_decode_kernel, dim3(1), dim3(1), 0, stream,
-                     moments.data_ptr<float>());
-  return {states, pdflats, actions, values, rewards, dones, boot_v, moments};
+  return rollout_launch<FAM>(a, P, x, epr, out_buf);
 }
 
 std::vector<torch::Tensor> rollout_run_mcat(

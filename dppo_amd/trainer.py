@@ -50,6 +50,7 @@ from .config import DPPOConfig, game_spaces
 from .envs.synthetic import BatchedSyntheticEnv, make_env
 from .models.mlp import PolicyValueMLP  # noqa: F401 (public engine surface)
 from .ops import gae_advantages, ppo_losses, PPOLossCoeffs
+from .ops.rollout_blob import rollout_blob
 from .parallel.comm import Comm, FlatBuffers
 from .utils.graphs import warm_and_capture
 from .utils.logging import ScalarLogger
@@ -366,19 +367,28 @@ class DPPOEngine:
                 a = torch.where(explore.unsqueeze(-1), rand_a, a)
         return a, v, pdflat
 
+    @staticmethod
+    def _env_switch(name: str, default: bool) -> bool:
+        """An on/off DPPO_* knob: '0' is off, any other value on, unset the
+        (measured) default."""
+        ov = os.environ.get(name)
+        return default if ov is None else ov != "0"
+
+    def _fits_rollout_kernel(self) -> bool:
+        """The family-independent limits of rollout.hip's kernel on the
+        synthetic env: 1-3 hidden layers of width <= 128, obs <= 512, env
+        rank <= 32."""
+        H = self.cfg.HIDDEN_SIZES
+        return (1 <= len(H) <= 3 and max(H) <= 128
+                and self.obs_space.shape[0] <= 512
+                and self.env.Vt.size(0) <= 32)
+
     def _can_fuse_rollout(self) -> bool:
         """Eligibility for the fused HIP rollout kernel (rollout.hip):
         Box/DiagGaussian policy, dims within kernel limits, fp32, GPU."""
-        c = self.cfg
         if self._physics or not self._hip_path("box"):
             return False
-        if not (1 <= len(c.HIDDEN_SIZES) <= 3):
-            return False
-        if max(c.HIDDEN_SIZES) > 128 or self.obs_space.shape[0] > 512:
-            return False
-        if self.act_space.shape[0] > 32 or self.env.Vt.size(0) > 32:
-            return False
-        return True
+        return self._fits_rollout_kernel() and self.act_space.shape[0] <= 32
 
     @torch.no_grad()
     def rollout_once(self) -> Tuple[RolloutBatch, Dict[str, float]]:
@@ -400,32 +410,22 @@ class DPPOEngine:
         dims within kernel limits, fp32, GPU.  Separate from
         _can_fuse_rollout(), which also gates the Box-only v3 rollout and
         graphed update."""
-        c = self.cfg
         if self._physics or not self._hip_path("discrete"):
             return False
-        if not (1 <= len(c.HIDDEN_SIZES) <= 3):
-            return False
-        if max(c.HIDDEN_SIZES) > 128 or self.obs_space.shape[0] > 512:
-            return False
-        if not (2 <= self.act_space.n <= 64) or self.env.Vt.size(0) > 32:
-            return False
-        return True
+        return self._fits_rollout_kernel() and 2 <= self.act_space.n <= 64
 
     def _use_rollout_cat(self) -> bool:
         """Dispatch for Discrete games: DPPO_ROLLOUT_CAT=0 forces the eager
         loop, =1 the fused kernel wherever eligible."""
         if not self._can_fuse_rollout_cat():
             return False
-        ov = os.environ.get("DPPO_ROLLOUT_CAT")
-        if ov is not None:
-            return ov != "0"
         # measured, T=64 (tools/rollout_cat_ab.py, profiles/r04_rollout_cat.txt):
         # CartPole (16,) eager 27.3 / 26.6 / 26.4 ms vs fused 0.42 / 0.94 /
         # 7.09 ms at E = 128 / 4096 / 65536; LunarLander (64,64) eager 27.7 /
         # 28.0 / 27.8 ms vs fused 0.54 / 1.22 / 9.78 ms; repeat spread < 1 %
         # on the fused arm.  No crossover in the measured range -> on
         # wherever eligible.
-        return True
+        return self._env_switch("DPPO_ROLLOUT_CAT", True)
 
     @property
     def _nvec(self):
@@ -439,15 +439,10 @@ class DPPOEngine:
         sum(nvec) <= 64, or MultiBinary with n <= 32; dims within kernel
         limits, fp32, GPU.  Its own function: _can_fuse_rollout_cat() stays
         False for these games."""
-        c = self.cfg
         if self._physics or not (self._hip_path("multidiscrete")
                                  or self._hip_path("multibinary")):
             return False
-        if not (1 <= len(c.HIDDEN_SIZES) <= 3):
-            return False
-        if max(c.HIDDEN_SIZES) > 128 or self.obs_space.shape[0] > 512:
-            return False
-        if self.env.Vt.size(0) > 32:
+        if not self._fits_rollout_kernel():
             return False
         if self._act_kind == "multidiscrete":
             nvec = self._nvec
@@ -461,9 +456,6 @@ class DPPOEngine:
         fused kernel wherever eligible."""
         if not self._can_fuse_rollout_multi():
             return False
-        ov = os.environ.get("DPPO_ROLLOUT_MULTI")
-        if ov is not None:
-            return ov != "0"
         # measured, T=64 (tools/rollout_multi_ab.py,
         # profiles/r10_rollout_multi.txt): MultiLever (32,) eager 32.8 / 34.7 /
         # 31.9 ms vs fused 0.50 / 1.10 / 8.56 ms at E = 128 / 4096 / 65536;
@@ -471,7 +463,7 @@ class DPPOEngine:
         # 9.92 ms; the widest min..max spread is 6.6 ms (eager) and 0.04 ms
         # (fused).  No crossover in the measured range -> on wherever
         # eligible.
-        return True
+        return self._env_switch("DPPO_ROLLOUT_MULTI", True)
 
     def _can_rollout_v3(self) -> bool:
         """Per-step GEMM rollout (v3): the T-step loop runs as pipelined
@@ -483,12 +475,10 @@ class DPPOEngine:
             return False
         if self.obs_space.shape[0] % 4 != 0:  # pipelined-GEMM staging
             return False
-        ov = os.environ.get("DPPO_ROLLOUT_V3")
-        if ov is not None:
-            return ov != "0"
         # measured crossover: fused 6.8 vs v3 9.1 ms at E=16384, fused
         # 13.0 vs v3 10.3 ms at E=32768 (tools/rollout_v3_ab.py)
-        return self.cfg.NUM_ENVS >= 32768
+        return self._env_switch("DPPO_ROLLOUT_V3",
+                                self.cfg.NUM_ENVS >= 32768)
 
     def _can_rollout_classic(self) -> bool:
         """Eligibility for the lane-per-env physics rollout
@@ -504,9 +494,6 @@ class DPPOEngine:
         eager loop, any other value the kernel wherever eligible."""
         if not self._can_rollout_classic():
             return False
-        ov = os.environ.get("DPPO_ROLLOUT_CLASSIC")
-        if ov is not None:
-            return ov != "0"
         # measured, T=64, ms per rollout_once() (tools/rollout_classic_ab.py,
         # profiles/r12_rollout_classic.txt): CartPole (16,) eager 34.7 / 35.0 /
         # 34.6 vs kernel 0.22 / 0.23 / 0.31 at E = 128 / 4096 / 65536;
@@ -549,7 +536,7 @@ class DPPOEngine:
         #   <1,3,2> VGPR 115 SGPR  99 LDS 34832 B at (64,64)  occ 4 (LDS: 1)
         #   <0,4,1> VGPR  65 SGPR  83 LDS   464 B at (16,)    occ 7
         #   <0,4,2> VGPR 118 SGPR 104 LDS 34832 B at (64,64)  occ 4 (LDS: 1)
-        return True
+        return self._env_switch("DPPO_ROLLOUT_CLASSIC", True)
 
     @torch.no_grad()
     def _rollout_once_hip_classic(self) -> Tuple[RolloutBatch, Dict[str, float]]:
@@ -559,39 +546,9 @@ class DPPOEngine:
         step + episode bookkeeping and resets for all T steps, into the out
         blob layouts of rollout_run_cat (K = the game's action count: 2 or
         3) / rollout_run (A = 1).  The env is chosen by env.ENV_ID inside the
-        family's binding; D, the observation width (2 for both MountainCars),
-        sizes the blob here exactly as the bindings do."""
-        from .ops import hip_ext
-
-        ext = hip_ext()
-        c, E, T = self.cfg, self.cfg.NUM_ENVS, self.cfg.MAX_EPOCH_STEPS
-        eps = self.exploration_rate()
-        env = self.env
-        seed = self._next_rollout_seed()
-        blob, offsets, dims = self._rollout_weight_blob()
-        D = self.obs_space.shape[0]
-        if self._discrete:
-            n_act = self.act_space.n
-            n_out = T * E * (2 + D + n_act + 3) + E + 5
-            run, bounds = ext.classic_rollout_cat, ()
-        else:
-            n_act = self.act_space.shape[0]
-            n_out = T * E * (D + 3 * n_act + 3) + E + 5
-            run, bounds = ext.classic_rollout_box, self._act_bounds()
-        out = self._rollout_outputs(n_out)
-        self._v3_acts_valid = False  # no recorded activations
-        self._wide_rollout_h_valid = False
-        (states, pdflats, actions, values, rewards, dones, boot_v,
-         moments) = run(
-            blob, offsets, dims, self._act_code,
-            env.ENV_ID, env.s, env.time_limit, *bounds, float(eps),
-            env.x, env.t, self.epr, T, n_act, seed, out,
-        )
-        self.classic_rollout_launches += 1
-        self.obs = env.x  # updated in place by the kernel
-        return self._finish_hip_rollout(
-            states, pdflats, actions, values, rewards, dones, boot_v,
-            moments, eps)
+        family's binding."""
+        return self._rollout_once_fused(
+            "discrete" if self._discrete else "box", physics=True)
 
     @torch.no_grad()
     def _rollout_weight_blob(self):
@@ -668,53 +625,55 @@ class DPPOEngine:
         return (float(self.act_space.low.flat[0]),
                 float(self.act_space.high.flat[0]))
 
-    def _rollout_once_fused(self, kind: str):
+    # policy kind -> (synthetic-env binding, physics-env binding, n_act of the
+    # action space as the bindings take it, whether they take action bounds)
+    _ROLLOUT_KINDS = {
+        "discrete": ("rollout_run_cat", "classic_rollout_cat",
+                     lambda sp: sp.n, False),
+        "multidiscrete": ("rollout_run_mcat", None,
+                          lambda sp: [int(n) for n in sp.nvec], False),
+        "multibinary": ("rollout_run_bern", None, lambda sp: sp.n, False),
+        "box": ("rollout_run", "classic_rollout_box",
+                lambda sp: sp.shape[0], True),
+    }
+
+    def _rollout_once_fused(self, kind: str, physics: bool = False):
         """The single-launch rollout of one policy family (`kind`, an
         _act_kind): Categorical, MultiCategorical, Bernoulli or DiagGaussian,
-        which also takes the action bounds."""
+        which also takes the action bounds; on the synthetic env
+        (rollout.hip) or, with `physics`, a classic-control one
+        (classic_rollout.hip).  The persistent out blob is sized by
+        ops/rollout_blob.py exactly as the bindings size theirs."""
         from .ops import hip_ext
 
-        ext = hip_ext()
         c, E = self.cfg, self.cfg.NUM_ENVS
         T = c.MAX_EPOCH_STEPS
         eps = self.exploration_rate()
         env = self.env
         seed = self._next_rollout_seed()
         blob, offsets, dims = self._rollout_weight_blob()
-        D = self.obs_space.shape[0]
-        if kind == "discrete":
-            n_act = self.act_space.n
-            # actions(int64) | states | logits | values | rewards | dones |
-            # boot | moments, in floats
-            n_out = T * E * (2 + D + n_act + 3) + E + 5
-            run, bounds = ext.rollout_run_cat, ()
-        elif kind == "multidiscrete":
-            n_act = self._nvec
-            # as above with C int64 actions and sum(nvec) logits per row
-            n_out = T * E * (2 * len(n_act) + D + sum(n_act) + 3) + E + 5
-            run, bounds = ext.rollout_run_mcat, ()
-        elif kind == "multibinary":
-            n_act = self.act_space.n
-            # Box's layout with n logits: states | logits | actions | ...
-            n_out = T * E * (D + 2 * n_act + 3) + E + 5
-            run, bounds = ext.rollout_run_bern, ()
+        synthetic, classic, n_act_of, bounded = self._ROLLOUT_KINDS[kind]
+        run = getattr(hip_ext(), classic if physics else synthetic)
+        n_act = n_act_of(self.act_space)
+        bounds = self._act_bounds() if bounded else ()
+        out = self._rollout_outputs(
+            rollout_blob(kind, T, E, self.obs_space.shape[0], n_act).numel)
+        self._v3_acts_valid = False  # these kernels do not record acts
+        if physics:
+            self._wide_rollout_h_valid = False
+            env_args, ablate = (env.ENV_ID, env.s, env.time_limit), ()
         else:
-            n_act = self.act_space.shape[0]
-            n_out = T * E * (D + 3 * n_act + 3) + E + 5
-            run, bounds = ext.rollout_run, self._act_bounds()
-        out = self._rollout_outputs(n_out)
-        self._v3_acts_valid = False  # fused kernel does not record acts
-        (states, pdflats, actions, values, rewards, dones, boot_v,
-         moments) = run(
-            blob, offsets, dims, self._act_code,
-            env.blob, env.rank_eff, env.horizons_i32,
-            float(env.NOISE), *bounds, float(eps),
-            env.x, env.t, self.epr, T, n_act, seed, out, 0,
+            env_args = (env.blob, env.rank_eff, env.horizons_i32,
+                        float(env.NOISE))
+            ablate = (0,)
+        views = run(
+            blob, offsets, dims, self._act_code, *env_args, *bounds,
+            float(eps), env.x, env.t, self.epr, T, n_act, seed, out, *ablate,
         )
+        if physics:
+            self.classic_rollout_launches += 1
         self.obs = env.x  # updated in place by the kernel
-        return self._finish_hip_rollout(
-            states, pdflats, actions, values, rewards, dones, boot_v,
-            moments, eps)
+        return self._finish_hip_rollout(*views, eps)
 
     def _finish_hip_rollout(self, states, pdflats, actions, values, rewards,
                             dones, boot_v, moments, eps):
@@ -1089,28 +1048,10 @@ class DPPOEngine:
         eps = self.exploration_rate()
         env = self.env
         seed = self._next_rollout_seed()
-        A = self.act_space.shape[0]
-        D = self.obs_space.shape[0]
-        P = 2 * A
-        out = self._rollout_outputs(T * E * (D + 3 * A + 3) + E + 5)
-        o = 0
-
-        def take(shape):
-            nonlocal o
-            n = 1
-            for sd in shape:
-                n *= sd
-            v = out.narrow(0, o, n).view(shape)
-            o += n
-            return v
-
-        states = take((T, E, D))
-        pdflats = take((T, E, P))
-        actions = take((T, E, A))
-        values = take((T, E))
-        rewards = take((T, E))
-        dones = take((T, E))
-        boot_v = take((E,))
+        lay = rollout_blob("box", T, E, self.obs_space.shape[0],
+                           self.act_space.shape[0])
+        (states, pdflats, actions, values, rewards, dones, boot_v,
+         _) = lay.views(self._rollout_outputs(lay.numel))
         v3 = self._v3_buffers()
         v3["seed_dev"].fill_(seed & 0xFFFFFFFF)
         v3["eps_dev"].fill_(float(eps))
@@ -1478,9 +1419,6 @@ class DPPOEngine:
         MultiBinary policies on the autograd update loop, any other value
         takes the fused MFMA update wherever _can_fuse_update() holds;
         unset = the measured default below."""
-        ov = os.environ.get("DPPO_UPDATE_DISC")
-        if ov is not None:
-            return ov != "0"
         # measured, T=64, ms per update() of 4 steps (tools/update_disc_ab.py,
         # profiles/r11_update_disc.txt): CartPole (16,) autograd 2.02 / 5.97 /
         # 56.5 vs fused 0.31 / 0.74 / 6.22 at E = 128 / 4096 / 65536;
@@ -1489,7 +1427,7 @@ class DPPOEngine:
         # (64,64) 2.39 / 9.72 / 81.5 vs 0.58 / 1.62 / 16.4.  Fused wins every
         # alternated pair (4.1x at the least; spreads < 10 % autograd, < 0.3 %
         # fused).  No crossover in the measured range -> on wherever eligible.
-        return True
+        return DPPOEngine._env_switch("DPPO_UPDATE_DISC", True)
 
     def update(self, batch: RolloutBatch, l_mul: float) -> None:
         """UPDATE_STEPS repeated full-batch steps on the same data
